@@ -1,6 +1,7 @@
 """Headline benchmark: pre-training volumes/sec of the ViT-B/16^3 (contrastive) MAE step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1 without a launcher: spawns N ranks itself)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                             (N > 1 without a launcher: spawns N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -8,12 +9,17 @@ A "step" = one full optimisation step of BASELINE config 2 (ViT-B/16^3 autoenc a
 scripts train it, i.e. ``contr_mae_vit_base_patch16``; synthetic BraTS-shape 96^3 x 4ch volumes,
 batch 4 per GPU, mask 0.75): forward (both views) + loss chain + backward + global grad norm +
 AdamW, with the gradient all-reduce over RCCL at N > 1.  Inputs are resident in HBM before the timed
-region.  Weights come from the product's own ``initialize_weights`` (seed 0); the same state dict is
-handed to the CPU oracle for the ``cpu_baseline`` / ``parity`` legs, the only place ``oracle/`` is
-imported.  Rank 0 prints ONE JSON line (contract in the task statement) carrying ``roofline`` (the
-GEMM kernel the step spends most time in, timed with HIP events on the launch stream in
-instrumented steps right after the timed region; plus ``encoder_attn_mlp_b8``, the north-star
-sub-total at batch 8) and, at N = 1, ``cpu_baseline``.
+region.  Weights come from the product's own ``initialize_weights`` (seed 0).  Rank 0 prints ONE JSON
+line (contract in the task statement).
+
+A plain run sets up, warms up, times the K steps and prints the line; ``--dump-outputs DIR`` then runs
+the timed path once more on the batch of the last timed step, from the seeded state of set-up, and
+writes what it computed (``step_outputs``) as ``DIR/<name>.npy``: the same on every run up to float
+round-off.  ``--full`` adds everything else to the line: ``roofline`` (the GEMM kernel the
+step spends most time in, timed with HIP events on the launch stream in instrumented steps right after
+the timed region; plus ``encoder_attn_mlp_b8``, the north-star sub-total at batch 8), the secondary data
+points under ``config.also_*``, the exchange diagnostics at N > 1 and, at N = 1, ``cpu_baseline`` and
+``parity`` (the same state dict handed to the CPU oracle, the only place ``oracle/`` is imported).
 """
 from __future__ import annotations
 
@@ -70,11 +76,21 @@ def parse(argv=None):
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--grad-comm', default=None, choices=['fp32', 'bf16'],
                     help='wire dtype of the gradient all-reduce at >1 GPU (default: the compute precision)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the secondary data points (plain MAE, batch 8 / 32, fp32 mode)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline figure: roofline, secondary data points, CPU baseline + parity, '
+                         'exchange diagnostics at N > 1 (a plain run sets up, warms up, times the steps and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, run the timed path once more on the last timed batch from the seeded state of '
+                         'set-up and write what it computed (losses, seeded samples of the updated parameters and of the gradients) '
+                         'to DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and parity legs')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip the secondary data points (plain MAE, batch 8 / 32, fp32 mode)')
     ap.add_argument('--cpu-steps', type=int, default=3)
-    ap.add_argument('--profile-steps', type=int, default=3, help='instrumented steps for the roofline block')
-    return ap.parse_args(argv)
+    ap.add_argument('--profile-steps', type=int, default=3, help='with --full: instrumented steps for the roofline block')
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 # ----------------------------------------------------------------------------- ranks
@@ -157,6 +173,49 @@ def device_batches(batch, dev, n=2, seed=77):
         v1 = (v1 - v1.mean(dim=(2, 3, 4), keepdim=True)) / v1.std(dim=(2, 3, 4), keepdim=True)
         out.append((v1.contiguous(), v2))
     return out
+
+
+DUMP_SAMPLE = 1 << 21      # elements of the parameter / gradient samples written by --dump-outputs (8 MB each in float32)
+
+
+def step_outputs(model, eng):
+    """What a caller of the timed step receives after it: the loss terms + global gradient norm, the updated parameters and the
+    step's gradients.  Parameters and gradients are sampled at DUMP_SAMPLE fixed positions (seeded) of their concatenation in
+    ``named_parameters`` order, so the sample does not depend on the engine's arena layout.  -> {name: float32 / float64 array}"""
+    names = [n for n, p in model.named_parameters() if p.requires_grad]
+    params = torch.cat([eng.p[n].reshape(-1) for n in names])
+    grads = torch.cat([eng.g[n].reshape(-1) for n in names])
+    n = params.numel()
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(n, (DUMP_SAMPLE,), generator=torch.Generator(device='cpu').manual_seed(0)).sort().values.to(params.device)
+        params, grads = params[idx], grads[idx]
+    return {'losses': eng.losses[:6].double().cpu().numpy(),      # [loss, raw_edge, recon, percep, contr, grad_norm]
+            'params_sample': params.float().cpu().numpy(), 'grads_sample': grads.float().cpu().numpy()}
+
+
+def state_snapshot(eng):
+    """Copies of everything a fused step reads and updates (the set ``_StepRunner._capture`` saves around its warm-up launch:
+    parameters, gradients, AdamW moments, predictor BatchNorm statistics, the device block with the applied-step count) and the
+    host's step count."""
+    keep = [eng.params, eng.grads] + ([eng.opt_state['exp_avg'], eng.opt_state['exp_avg_sq']] if eng.opt_state else [])
+    keep += [t for k, t in eng.buffers.items() if k.startswith('predictor.1.')]
+    keep.append(eng.hp)
+    return keep, [t.clone() for t in keep], eng.opt_step
+
+
+def restore_state(eng, snap):
+    keep, saved, opt_step = snap
+    for t, s in zip(keep, saved):
+        t.copy_(s)
+    eng.opt_step = opt_step
+    eng.refresh_shadow(force=True)     # the bf16 / two-plane weight copies follow the restored fp32 arena
+
+
+def write_outputs(outdir, outs):
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in outs.items():
+        np.save(os.path.join(outdir, f'{name}.npy'), a)
 
 
 def run_steps(model, eng, batches, contr, batch, graph, warm, steps):
@@ -518,6 +577,7 @@ def main():
     batches = [(a.to(dev), b.to(dev)) for a, b in cpu_batches]
     L = eng.cfg.num_patches
     noises = [masking_noise(args.batch, L, seed=4321 + rank + i) for i in range(len(batches))]
+    snap = state_snapshot(eng) if args.dump_outputs else None     # the seeded state of set-up, for the step --dump-outputs writes
 
     def timed_leg(native):
         """W warm-up + K timed steps of the headline workload through one gradient-exchange route; -> (seconds, first-step
@@ -562,7 +622,7 @@ def main():
         red = model._reducer
         desc = None
         diag = None
-        if red is not None and red.active:
+        if args.full and red is not None and red.active:
             # VERDICT r3 item 7 — make the one hardware run say WHY: per-bucket all-reduce time on the communication stream
             # (host-issued route: events around every collective), and the same step with the exchange switched off on the same
             # ranks (replicas drift apart: measurement only, nothing after this leg uses them without a fresh broadcast)
@@ -607,7 +667,20 @@ def main():
             if native:
                 desc['vitae_ddp_world_size'] = int(_lib.vitae_ddp_world_size())
                 assert desc['vitae_ddp_world_size'] == world, (desc['vitae_ddp_world_size'], world)
-        return el, first, eng.losses.cpu().tolist(), desc
+        last = eng.losses.cpu().tolist()
+        outs = None
+        if snap is not None:
+            # --dump-outputs: the timed path (same runner, same graph) on the batch of the last timed step, started from the
+            # seeded state of set-up with seeded masking noise.  The steps before it are not replayed into what is written: the
+            # kernels sum some gradients with float atomics, and a few dozen AdamW steps grow those last-bit differences well
+            # past round-off, while one step from a fixed state reproduces to round-off run after run.
+            restore_state(eng, snap)
+            n1, n2 = noises[(args.steps - 1) % len(noises)]
+            model.set_masking_noise(*((n1, n2) if contr else (n1,)))
+            step(args.steps - 1)
+            torch.cuda.synchronize()
+            outs = step_outputs(model, eng) if rank == 0 else None
+        return el, first, last, desc, outs
 
     # N > 1 (the driver's one scaling run): BOTH exchange routes in the same invocation — host-issued collectives between
     # per-phase graphs (default) and RCCL inside the step graph (vitae_ddp_*); the faster is the reported value, the other sits in
@@ -621,14 +694,16 @@ def main():
     also_exchange = None
     if ddp_on and ONE_GPU:
         also_exchange = {'skipped': 'native RCCL leg needs one GPU per rank (plumbing mode: all ranks on one GPU over gloo)'}
-    elapsed, first_gpu, last, exchange = legs[0]
+    elapsed, first_gpu, last, exchange, outs = legs[0]
+    if outs is not None:
+        write_outputs(args.dump_outputs, outs)
     forked = eng.forked_branches()      # (of the timed workload: the extra points below rebind the workspace)
     ms = elapsed / args.steps * 1e3
     value = world * args.batch * args.steps / elapsed
 
     # ---- roofline of the dominant kernel (the MFMA GEMM kernels of csrc/gemm_glds.hip / gemm_bf16.hip / gemm.hip)
     roof = None
-    if rank == 0 and args.profile_steps > 0:
+    if args.full and rank == 0 and args.profile_steps > 0:
         recs, overhead = instrumented_steps(model, eng, batches, contr, args.batch, args.profile_steps, dev,
                                             phases_only=world > 1)
         roof = roofline_block(args, recs, overhead, ms, world)
@@ -636,7 +711,7 @@ def main():
         dist.barrier()
 
     extra = {}
-    single = rank == 0 and world == 1 and not force_ddp and not args.no_extra
+    single = args.full and rank == 0 and world == 1 and not force_ddp and not args.no_extra
     if single and args.batch != 8 and args.precision == 'bf16':
         try:
             extra['also_batch8'], enc = encoder_attn_mlp_point(args, dev, model, eng, contr)
@@ -691,7 +766,7 @@ def main():
                 extra[f'also_cfg{which}'] = {'error': repr(e)[:200]}
 
     cpu, parity = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, first_cpu = cpu_baseline(args, cpu_batches, sd_cpu, noises)
         ref_total, ref_recon = first_cpu['loss'], first_cpu['reconstruction_loss']
         got_total, got_recon = first_gpu[0] + (first_gpu[4] if contr else 0.0), first_gpu[2]
@@ -785,6 +860,8 @@ def main():
                     out['value'] = round(world * args.batch * args.steps / leg[0], 2)
                     out['ms_per_step'] = round(leg[0] / args.steps * 1e3, 3)
                     out['config']['final_losses'] = [round(x, 6) for x in leg[2][:6]]
+                    if leg[4] is not None:
+                        write_outputs(args.dump_outputs, leg[4])
                 else:
                     out['config']['also_exchange'] = leg[3]
         except Exception as e:

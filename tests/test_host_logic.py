@@ -204,3 +204,14 @@ def test_bench_rank_plumbing():
     with pytest.raises(SystemExit):
         bench.rank_layout(bench.parse(['--gpus', '1']), env={'WORLD_SIZE': '8', 'RANK': '3', 'LOCAL_RANK': '3'})
     assert bench.rank_layout(args, env={'WORLD_SIZE': '2', 'RANK': '1', 'LOCAL_RANK': '1'}) == (2, 1, 1)
+
+
+def test_bench_options():
+    """bench.py: the secondary measurements are opt-in (--full), --dump-outputs takes a directory, and --steps counts timed steps."""
+    import bench
+    a = bench.parse(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(['--full', '--dump-outputs', 'out'])
+    assert a.full and a.dump_outputs == 'out'
+    with pytest.raises(SystemExit):
+        bench.parse(['--steps', '0'])

@@ -1,13 +1,14 @@
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/r6
-timeout 2400 python -m pytest tests -x -q -m gpu > gpurun_out/r6/gpu_tests_full.txt 2>&1
+# The GPU test suite, then the full benchmark line with its secondary points; logs go to the directory given as the argument.
+cd "$(dirname "$0")/../.."; O=${1:?usage: tools/probes/r6_full.sh OUTPUT_DIR}; mkdir -p "$O"
+timeout 2400 python -m pytest tests -x -q -m gpu > $O/gpu_tests_full.txt 2>&1
 echo tests rc=$?
-grep -n "Error\|FAILED\|passed\|failed" gpurun_out/r6/gpu_tests_full.txt | head -10
-( time python bench.py ) > gpurun_out/r6/bench_default.log 2>&1
-grep '^{' gpurun_out/r6/bench_default.log | tail -1 > gpurun_out/r6/bench_line.json
-grep real gpurun_out/r6/bench_default.log
+grep -n "Error\|FAILED\|passed\|failed" $O/gpu_tests_full.txt | head -10
+( time python bench.py --full ) > $O/bench_default.log 2>&1
+grep '^{' $O/bench_default.log | tail -1 > $O/bench_line.json
+grep real $O/bench_default.log
 python - <<PY
 import json
-d=json.load(open('gpurun_out/r6/bench_line.json'))
+d=json.load(open('$O/bench_line.json'))
 print(d['value'], d['ms_per_step'])
 c=d['config']
 for k in ('also_batch8','also_batch32','also','also_fp32','also_fp32x3','also_epoch_loop','also_p8','also_cfg4','also_cfg5'):
