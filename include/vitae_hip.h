@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define VITAE_ABI_VERSION 48
+#define VITAE_ABI_VERSION 49
 
 /* matrix-core arithmetic of the dense contractions */
 #define VITAE_PREC_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32 (the reference's precision, autocast off at utils/train_one_epoch.py:50) */
@@ -292,6 +292,17 @@ int vitae_encoder_assemble_bwd(const float* dx, float* dtok, void* dtok_bf16, fl
 /* out[B,D] = mean_{n >= first} x[B,N,D]: global average pool over the patch tokens of the encoder-only model
  * (model/vit.py:277-278, first = 1 skips the cls token) */
 int vitae_mean_pool_tokens(const float* x, float* out, int B, int N, int D, int first, void* stream);
+/* ---- encoder-only model, training (fine-tuning VisionTransformer3D) ---------------------------------
+ * Backward of x = cat(cls_token, tok) + pos_embed with a TRAINABLE position table (model/vit.py:269-272), dx [B, L+1, D]:
+ * dtok[B*L, D] = dx[:, 1:] (fp32 and / or a bf16 copy; either may be NULL), dpos[L+1, D] (+)= sum_b dx[b], dcls[D] (+)= sum_b dx[b, 0]
+ * (the cls row feeds both cls_token and pos_embed[0]; dpos / dcls may be NULL for a frozen parameter).  accumulate = 0 overwrites.
+ * The batch is summed in sample order inside one thread: no atomics, bitwise reproducible.  D % 4 == 0, 16-byte aligned arrays. */
+int vitae_vit_assemble_bwd(const float* dx, float* dtok, void* dtok_bf16, float* dpos, float* dcls, int B, int L, int D,
+                           int accumulate, void* stream);
+/* Backward of the token reduction in front of the classifier (model/vit.py:277-282), dsel [B, D] -> dx [B, N, D], every element
+ * written: mode 1 (global pool, x[:, 1:].mean(1)): rows 1..N-1 = dsel[b] / (N - 1), row 0 = 0; mode 0 (cls row, x[:, 0]):
+ * row 0 = dsel[b], the others 0.  D % 4 == 0, 16-byte aligned arrays. */
+int vitae_token_select_bwd(const float* dsel, float* dx, int B, int N, int D, int mode, void* stream);
 /* xd[B,L+1,Dd]: mask-token fill + unshuffle + decoder_pos_embed (model/vit_autoenc.py:184-190) */
 int vitae_decoder_assemble_fwd(const float* e, const float* mask_token, const float* dpos, const int* ids_restore,
                                float* xd, int B, int L, int keep, int Dd, void* stream);

@@ -23,6 +23,9 @@ _ALIASES = {
     'utils.lr_sched': 'vit_ae_plus_plus_amd.utils.lr_sched',
     'utils.train_one_epoch': 'vit_ae_plus_plus_amd.utils.train_one_epoch',
     'utils.custom_loss': 'vit_ae_plus_plus_amd.utils.custom_loss',
+    'utils.lr_decay': 'vit_ae_plus_plus_amd.utils.lr_decay',
+    'post_training_utils': 'vit_ae_plus_plus_amd.post_training_utils',
+    'post_training_utils.fine_tune_epoch': 'vit_ae_plus_plus_amd.post_training_utils.fine_tune_epoch',
 }
 
 

@@ -127,8 +127,8 @@ class HipEncoder:
             lib.vitae_sdpa_fwd(_ptr(b['qkv']), _ptr(b['o']), _ptr(b['lse']), B, N, m.num_heads, self.hd, self.stream)
 
     # ------------------------------------------------------------------ forward
-    @torch.no_grad()
-    def forward_features(self, x: torch.Tensor) -> torch.Tensor:
+    def _begin(self, x: torch.Tensor):
+        """Checks the input against the module and fixes the geometry of this call (device, stream, parameter table, sizes)."""
         m = self.m
         if not x.is_cuda:
             raise VitaeError(f'forward_features: input is on {x.device}; this package computes on MI355X only (no CPU fallback)')
@@ -142,12 +142,18 @@ class HipEncoder:
         B, C, Lz, Hy, Wx = x.shape
         assert (Lz, Hy, Wx) == tuple(pe.volume_size), \
             f"Volume image size ({Lz}*{Hy}*{Wx}) doesn't match model ({pe.volume_size[0]}*{pe.volume_size[1]}*{pe.volume_size[2]})."
-        L, D = pe.num_patches, m.embed_dim
-        N, M = L + 1, B * (L + 1)
         self.P = C * ps ** 3
-        self.hidden = m.blocks[0].mlp.fc1.out_features if len(m.blocks) else D
-        self.hd = D // m.num_heads
+        self.hidden = m.blocks[0].mlp.fc1.out_features if len(m.blocks) else m.embed_dim
+        self.hd = m.embed_dim // m.num_heads
         self.eps = m.ln_eps
+        return B, C, Lz, Hy, Wx, ps
+
+    @torch.no_grad()
+    def forward_features(self, x: torch.Tensor) -> torch.Tensor:
+        m = self.m
+        B, C, Lz, Hy, Wx, ps = self._begin(x)
+        L, D = m.patch_embed.num_patches, m.embed_dim
+        N, M = L + 1, B * (L + 1)
         H, P = self.hidden, self.P
         self.act16 = (self.prec == PREC['bf16'] and all(v % 64 == 0 for v in (D, H, P)) and self.hd in (32, 64))
         self._alloc(B)
@@ -190,3 +196,201 @@ class HipEncoder:
             b['pool'].copy_(cur.view(B, N, D)[:, 0])
             self._ln(b['pool'], 'norm.', b['feat'], None, B, D)
         return b['feat'].clone()
+
+
+EPI_DGELU, EPI_AUX_DERIV = _C['VITAE_EPI_DGELU'], _C['VITAE_EPI_AUX_DERIV']
+_EMBED = ('cls_token', 'pos_embed', 'patch_embed.proj.weight', 'patch_embed.proj.bias')
+
+
+class HipEncoderTrainer(HipEncoder):
+    """Training counterpart of ``HipEncoder`` (fine-tuning, reference post_training_utils/fine_tune_epoch.py:34-100):
+    ``forward_keep`` runs the same launch sequence on the generic Linear launchers and keeps, per block, what the backward
+    reads; ``backward`` walks the blocks from the top in the launch order of ``HipMAEEngine._block_bwd`` — eager launches
+    on the current stream, no side streams, no graph capture.
+
+    The kept activations are allocated per call and returned to the caller (who hangs them on the autograd context), so any
+    number of forwards may precede a backward.  Only split-K scratch and the patch index table live on the trainer.
+    Gradients are produced for the parameters named in ``needs`` only: a frozen Linear has no weight-gradient launch, and
+    blocks below the lowest trainable parameter are neither kept nor walked.  ``stats`` counts the calls and the bytes the
+    last forward kept (tests read it; nothing else does)."""
+
+    WS_FLOATS = 1 << 24        # split-K scratch, 64 MiB (as the training engine's)
+
+    def __init__(self, module, precision: str = 'fp32'):
+        super().__init__(module, precision)
+        self.act16 = False     # the bf16-activation route is inference-only
+        self.stats = {'forwards': 0, 'backwards': 0, 'kept_bytes': 0}
+
+    def _workspace(self, B: int, L: int):
+        if self._B != self.device:          # scratch does not depend on the batch: forwards of different sizes may interleave
+            self._B = self.device
+            self.buf = {'ws': torch.empty(self.WS_FLOATS, dtype=torch.float32, device=self.device)}
+        if ('ids', B) not in self.buf:
+            self.buf['ids', B] = torch.arange(L, dtype=torch.int32, device=self.device).repeat(B, 1).contiguous()
+        return self.buf['ids', B]
+
+    def _f(self, *shape):
+        return torch.empty(*shape, dtype=torch.float32, device=self.device)
+
+    def _z(self, *shape):
+        return torch.zeros(*shape, dtype=torch.float32, device=self.device)
+
+    @staticmethod
+    def lowest_trainable(needs: Dict[str, bool], depth: int) -> Tuple[bool, int]:
+        """(an embedding parameter is trainable, index of the lowest block the backward has to reach: ``depth`` = none)."""
+        embed = any(needs.get(n, False) for n in _EMBED)
+        if embed:
+            return True, 0
+        lo = depth
+        for n, need in needs.items():
+            if need and n.startswith('blocks.'):
+                lo = min(lo, int(n.split('.')[1]))
+        return False, lo
+
+    # ------------------------------------------------------------------ forward
+    def _ln_keep(self, x, pre, y, mean, rstd, M, D):
+        lib.vitae_layernorm_fwd(_ptr(x), _ptr(self._param(pre + 'weight')), _ptr(self._param(pre + 'bias')), _ptr(y), None,
+                                _ptr(mean), _ptr(rstd), M, D, self.eps, self.stream)
+
+    def _block_keep(self, q, x_in, B, N, D, H):
+        f, M, heads = self._f, B * N, self.m.num_heads
+        k = {'x_in': x_in, 'mean1': f(M), 'rstd1': f(M), 'y1': f(M, D), 'qkv': f(M, 3 * D), 'o': f(M, D), 'lse': f(B * heads * N),
+             'xmid': f(M, D), 'mean2': f(M), 'rstd2': f(M), 'y2': f(M, D), 'hpre': f(M, H), 'act': f(M, H)}
+        x_out = f(M, D)
+        self._ln_keep(x_in, q + 'norm1.', k['y1'], k['mean1'], k['rstd1'], M, D)
+        self._lin(k['y1'], q + 'attn.qkv.weight', q + 'attn.qkv.bias', k['qkv'], M, 3 * D, D)
+        if self.prec == PREC['bf16'] and self.hd in (32, 64):
+            lib.vitae_sdpa_mfma_fwd(_ptr(k['qkv']), _ptr(k['o']), None, _ptr(k['lse']), B, N, heads, self.hd, self.stream)
+        else:
+            lib.vitae_sdpa_fwd(_ptr(k['qkv']), _ptr(k['o']), _ptr(k['lse']), B, N, heads, self.hd, self.stream)
+        self._lin(k['o'], q + 'attn.proj.weight', q + 'attn.proj.bias', k['xmid'], M, D, D, res=x_in)
+        self._ln_keep(k['xmid'], q + 'norm2.', k['y2'], k['mean2'], k['rstd2'], M, D)
+        # aux <- GELU'(pre-activation): what the backward multiplies by (as the training engine keeps it)
+        self._lin(k['y2'], q + 'mlp.fc1.weight', q + 'mlp.fc1.bias', k['act'], M, H, D, epi=EPI_GELU | EPI_AUX_DERIV, aux=k['hpre'])
+        self._lin(k['act'], q + 'mlp.fc2.weight', q + 'mlp.fc2.bias', x_out, M, D, H, res=k['xmid'])
+        return k, x_out
+
+    def forward_keep(self, x: torch.Tensor, needs: Dict[str, bool]):
+        """-> (features [B, D], kept): ``kept`` is what ``backward`` needs, owned by the caller."""
+        m = self.m
+        B, C, Lz, Hy, Wx, ps = self._begin(x)
+        L, D, H, P = m.patch_embed.num_patches, m.embed_dim, self.hidden, self.P
+        N, M, depth = L + 1, B * (L + 1), len(m.blocks)
+        if D % 4:
+            raise VitaeError('embed_dim must be a multiple of 4')
+        ids = self._workspace(B, L)
+        f, st = self._f, self.stream
+        embed, lo = self.lowest_trainable(needs, depth)
+        xc = x.detach().contiguous().float()
+        patches, tok, cur = f(B * L, P), f(B * L, D), f(M, D)
+        lib.vitae_gather_patches(_ptr(xc), _ptr(ids), _ptr(patches), None, B, C, Lz, Hy, Wx, ps, L, st)
+        self._lin(patches, 'patch_embed.proj.weight', 'patch_embed.proj.bias', tok, B * L, D, P)
+        lib.vitae_encoder_assemble_fwd(_ptr(tok), _ptr(self._param('cls_token')), _ptr(self._param('pos_embed')), _ptr(ids),
+                                       _ptr(cur), B, L, L, D, st)
+        blocks = {}
+        for i in range(depth):
+            kb, cur = self._block_keep(f'blocks.{i}.', cur, B, N, D, H)
+            if i >= lo:
+                blocks[i] = kb
+        pool, feat, mean, rstd = f(B, D), f(B, D), f(B), f(B)
+        if m.global_pool:
+            lib.vitae_mean_pool_tokens(_ptr(cur), _ptr(pool), B, N, D, 1, st)
+            self._ln_keep(pool, 'fc_norm.', feat, mean, rstd, B, D)
+        else:
+            pool.copy_(cur.view(B, N, D)[:, 0])
+            self._ln_keep(pool, 'norm.', feat, mean, rstd, B, D)
+        kept = {'geom': (B, L, D, H, P), 'needs': dict(needs), 'params': self.sd, 'embed': embed, 'lo': lo, 'blocks': blocks,
+                'versions': {n: p._version for n, p in self.sd.items() if not n.startswith('head.')},
+                'patches': patches if needs.get('patch_embed.proj.weight') else None, 'pool': pool, 'mean': mean, 'rstd': rstd}
+        self.stats['forwards'] += 1
+        self.stats['kept_bytes'] = 4 * (sum(t.numel() for kb in blocks.values() for t in kb.values())
+                                        + sum(t.numel() for t in (kept['patches'], pool, mean, rstd) if t is not None))
+        return feat, kept
+
+    # ------------------------------------------------------------------ backward
+    def _split_bwd(self, M, N, K):
+        """Split of the reduction (length K) of a backward GEMM with an [M, N] result, fitted to the scratch buffer."""
+        key = ('b', M, N, K)
+        s = self._split.get(key)
+        if s is None:
+            s = (lib.vitae_gemm_bf16x3_pick_split_k if self.prec == PREC['fp32x3'] else lib.vitae_gemm_pick_split_k)(M, N, K)
+            while s > 1 and s * M * N > self.buf['ws'].numel():
+                s -= 1
+            self._split[key] = s
+        return s
+
+    def _lin_bwd(self, grads, needs, dy, wname, bname, x, dx, M, N, K, epi=EPI_NONE, aux=None):
+        """Backward of y = x W^T + b given dy [M, N]: dW = dy^T x and db = colsum(dy) for trainable parameters only,
+        dx = epi(dy W) when ``dx`` is given."""
+        ws = self.buf['ws'].data_ptr()
+        if needs.get(wname):
+            w = self._param(wname)
+            dw = grads[wname] = torch.empty_like(w)
+            lib.vitae_linear_bwd_weight(self.prec, _ptr(dy), _ptr(x), _ptr(dw), M, N, K, 0, self._split_bwd(N, K, M), ws, self.stream)
+        if needs.get(bname):
+            db = grads[bname] = self._z(N)          # the column-sum launcher adds
+            lib.vitae_colsum_accum(_ptr(dy), N, _ptr(db), M, N, self.stream)
+        if dx is not None:
+            lib.vitae_linear_bwd_input(self.prec, _ptr(dy), _ptr(self._param(wname)), _ptr(dx), M, N, K, epi, _ptr(aux), 0,
+                                       self._split_bwd(M, K, N), ws, self.stream)
+
+    def _ln_bwd(self, grads, needs, dy, x, pre, mean, rstd, dx, M, D, dx_accumulate):
+        dw, db = self._z(D), self._z(D)             # the launcher adds its column partials
+        lib.vitae_layernorm_bwd(_ptr(dy), _ptr(x), _ptr(self._param(pre + 'weight')), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dw),
+                                _ptr(db), None, None, M, D, dx_accumulate, self.stream)
+        if needs.get(pre + 'weight'):
+            grads[pre + 'weight'] = dw
+        if needs.get(pre + 'bias'):
+            grads[pre + 'bias'] = db
+
+    def backward(self, kept, dfeat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """d loss / d features [B, D] -> {parameter name: gradient} for the trainable parameters of the encoder."""
+        m = self.m
+        B, L, D, H, P = kept['geom']
+        N, M, depth, heads = L + 1, B * (L + 1), len(m.blocks), m.num_heads
+        self.device = dfeat.device
+        self.stream = torch.cuda.current_stream(dfeat.device).cuda_stream
+        self.sd = kept['params']
+        stale = [n for n, v in kept['versions'].items() if self.sd[n]._version != v]
+        if stale:       # the backward reads the weights again: they must be the ones the forward used (as autograd checks for its own ops)
+            raise VitaeError(f'parameters were modified in place between forward and backward: {stale[:3]} ...')
+        self._workspace(B, L)
+        needs, f, st = kept['needs'], self._f, self.stream
+        grads: Dict[str, torch.Tensor] = {}
+        dfeat = dfeat.contiguous().float()
+        dpool = f(B, D)
+        self._ln_bwd(grads, needs, dfeat, kept['pool'], 'fc_norm.' if m.global_pool else 'norm.', kept['mean'], kept['rstd'],
+                     dpool, B, D, 0)
+        self.stats['backwards'] += 1
+        embed, lo = kept['embed'], kept['lo']
+        if not embed and lo >= depth:
+            return grads
+        dx = f(M, D)
+        lib.vitae_token_select_bwd(_ptr(dpool), _ptr(dx), B, N, D, 1 if m.global_pool else 0, st)
+        dh, dy, do, dqkv, delta = f(M, H), f(M, D), f(M, D), f(M, 3 * D), f(B * heads * N)
+        mfma = self.prec == PREC['bf16'] and self.hd in (32, 64)
+        for i in range(depth - 1, lo - 1, -1):
+            q, k = f'blocks.{i}.', kept['blocks'][i]
+            self._lin_bwd(grads, needs, dx, q + 'mlp.fc2.weight', q + 'mlp.fc2.bias', k['act'], dh, M, D, H,
+                          epi=EPI_DGELU | EPI_AUX_DERIV, aux=k['hpre'])
+            self._lin_bwd(grads, needs, dh, q + 'mlp.fc1.weight', q + 'mlp.fc1.bias', k['y2'], dy, M, H, D)
+            self._ln_bwd(grads, needs, dy, k['xmid'], q + 'norm2.', k['mean2'], k['rstd2'], dx, M, D, 1)
+            self._lin_bwd(grads, needs, dx, q + 'attn.proj.weight', q + 'attn.proj.bias', k['o'], do, M, D, D)
+            if mfma:
+                lib.vitae_sdpa_mfma_bwd(_ptr(k['qkv']), _ptr(k['o']), _ptr(do), _ptr(k['lse']), _ptr(dqkv), None, None, _ptr(delta),
+                                        B, N, heads, self.hd, st)
+            else:
+                lib.vitae_sdpa_bwd(_ptr(k['qkv']), _ptr(k['o']), _ptr(do), _ptr(k['lse']), _ptr(dqkv), _ptr(delta), B, N, heads,
+                                   self.hd, st)
+            self._lin_bwd(grads, needs, dqkv, q + 'attn.qkv.weight', q + 'attn.qkv.bias', k['y1'], dy, M, 3 * D, D)
+            self._ln_bwd(grads, needs, dy, k['x_in'], q + 'norm1.', k['mean1'], k['rstd1'], dx, M, D, 1)
+        if embed:
+            patch = needs.get('patch_embed.proj.weight') or needs.get('patch_embed.proj.bias')
+            dtok = f(B * L, D) if patch else None
+            dpos = grads['pos_embed'] = torch.empty_like(self._param('pos_embed')) if needs.get('pos_embed') else None
+            dcls = grads['cls_token'] = torch.empty_like(self._param('cls_token')) if needs.get('cls_token') else None
+            lib.vitae_vit_assemble_bwd(_ptr(dx), _ptr(dtok), None, _ptr(dpos), _ptr(dcls), B, L, D, 0, st)
+            if patch:
+                self._lin_bwd(grads, needs, dtok, 'patch_embed.proj.weight', 'patch_embed.proj.bias', kept['patches'], None,
+                              B * L, D, P)
+        return {n: g for n, g in grads.items() if g is not None}

@@ -5,7 +5,8 @@ In this package the modules are *parameter containers*: they own tensors under t
 state-dict keys (``proj.weight``, ``attn.qkv.weight``, ``mlp.fc1.bias`` ...) so checkpoints
 round-trip, while the arithmetic of a whole model is sequenced by ``HipMAEEngine`` over
 libvitae_hip.so.  Their stand-alone ``forward`` methods run the same HIP kernels op by op
-(inference only: used by feature extraction, not by the training hot path).
+(without autograd: training goes through ``VisionTransformer3D``, whose encoder is one autograd node,
+or through the masked autoencoders).
 """
 from __future__ import annotations
 
@@ -31,8 +32,8 @@ def _require_hip(x, what):
         raise VitaeError(f'{what}: input is on {x.device}; this package computes on MI355X only '
                          f'(no CPU fallback).')
     if torch.is_grad_enabled() and x.requires_grad:
-        raise VitaeError(f'{what}: stand-alone module forward is inference-only; training goes through '
-                         f'MaskedAutoencoderViT / ContrastiveMAEViT')
+        raise VitaeError(f'{what}: the stand-alone module forward has no backward; training goes through '
+                         f'VisionTransformer3D (fine-tuning) or MaskedAutoencoderViT / ContrastiveMAEViT (pre-training)')
 
 
 def hip_linear(x, weight, bias, epi=0, residual=None, precision=0):
@@ -160,6 +161,65 @@ class Block(nn.Module):
         return self.mlp(hip_layernorm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps), residual=x)
 
 
+class _EncoderFunction(torch.autograd.Function):
+    """``apply(trainer, names, x, *params) -> features [B, D]``: the whole encoder of ``VisionTransformer3D`` as one autograd
+    node.  Forward keeps the activations on the context; backward returns one gradient per parameter (``None`` for frozen
+    ones) and none for the input volume."""
+
+    @staticmethod
+    def forward(ctx, trainer, names, x, *params):
+        needs = {n: bool(r) for n, r in zip(names, ctx.needs_input_grad[3:])}
+        feat, kept = trainer.forward_keep(x, needs)
+        ctx.trainer, ctx.names, ctx.kept = trainer, names, kept
+        return feat
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dfeat):
+        if ctx.kept is None:
+            raise VitaeError('VisionTransformer3D: backward called twice on one forward (activations are released after the first)')
+        grads = ctx.trainer.backward(ctx.kept, dfeat)
+        ctx.kept = None
+        return (None, None, None) + tuple(grads.get(n) for n in ctx.names)
+
+
+class _HeadFunction(torch.autograd.Function):
+    """Classifier head ``logits = f W^T + b`` on the HIP GEMM launchers, forward and backward (no vendor BLAS).  The GEMMs
+    move four columns at a time, so the class dimension is padded to a multiple of 4 with zero rows / columns around them."""
+
+    @staticmethod
+    def forward(ctx, f, weight, bias, prec):
+        f = f.contiguous().float()
+        ctx.save_for_backward(f, weight)
+        ctx.prec, ctx.has_bias = prec, bias is not None
+        return hip_linear(f, weight, bias, precision=prec)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        f, weight = ctx.saved_tensors
+        (B, D), C = f.shape, weight.shape[0]
+        Cp = (C + 3) // 4 * 4
+        st, prec = _stream(f), ctx.prec
+        dyp = torch.zeros(B, Cp, dtype=torch.float32, device=f.device)
+        dyp[:, :C] = dy
+        df = dw = db = None
+        if ctx.needs_input_grad[0]:
+            wp = torch.zeros(Cp, D, dtype=torch.float32, device=f.device)
+            wp[:C] = weight.detach()
+            df = torch.empty_like(f)
+            lib.vitae_linear_bwd_input(prec, dyp.data_ptr(), wp.data_ptr(), df.data_ptr(), B, Cp, D, 0, None, 0, 1, None, st)
+        if ctx.needs_input_grad[1]:
+            dwp = torch.empty(Cp, D, dtype=torch.float32, device=f.device)
+            lib.vitae_linear_bwd_weight(prec, dyp.data_ptr(), f.data_ptr(), dwp.data_ptr(), B, Cp, D, 0, 1, None, st)
+            dw = dwp[:C].contiguous()
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            dbp = torch.zeros(Cp, dtype=torch.float32, device=f.device)      # the column-sum launcher adds
+            lib.vitae_colsum_accum(dyp.data_ptr(), Cp, dbp.data_ptr(), B, Cp, st)
+            db = dbp[:C].contiguous()
+        return df, dw, db, None
+
+
 def _init_vit_weights(module: nn.Module, name: str = '', head_bias: float = 0.):
     """The reference's default ('') init scheme (model/vit.py:14-46): Linear weights trunc-normal(std .02) with zero
     bias, the classifier head zero, LayerNorm (1, 0); convolutions keep PyTorch's default."""
@@ -178,15 +238,25 @@ def _init_vit_weights(module: nn.Module, name: str = '', head_bias: float = 0.):
 
 class VisionTransformer3D(nn.Module):
     """Encoder-only 3-D ViT that consumes the pre-trained weights (reference model/vit.py:147-298): same constructor,
-    state-dict keys and ``forward_features`` / ``forward`` results; the arithmetic runs on the HIP kernels through
-    ``HipEncoder`` (inference: feature extraction, utils/feature_extraction.py).  Not covered: the DeiT distillation
-    token/head, ``representation_size`` pre-logits, non-zero dropout / stochastic depth, and back-propagation
-    (fine-tuning) — the constructor or the call says so instead of computing something else.
+    state-dict keys and ``forward_features`` / ``forward`` results; the arithmetic runs on the HIP kernels.
+
+    Inference (``eval()`` mode or ``torch.no_grad()``: feature extraction, utils/feature_extraction.py) goes through
+    ``HipEncoder`` and returns a detached result.  Training (``train()`` mode, gradients enabled, at least one trainable
+    parameter: fine-tuning, post_training_utils/fine_tune_epoch.py) goes through ``HipEncoderTrainer``: the encoder is one
+    autograd node, the head a second one, so ``loss.backward()`` leaves ordinary ``.grad`` tensors and optimisers, gradient
+    accumulation, clipping and checkpoints need nothing special.  Frozen parameters get no gradient launch; with the whole
+    encoder frozen (``--fix_backbone``) the inference path runs and nothing is kept.
+
+    Deviations from the reference: it differentiates in ``eval()`` mode too, this module does not (a call in ``eval()``
+    mode is inference).  ``drop_path_rate`` is accepted and has no effect, in training mode as well — the reference ignores
+    it too (``DropPath`` is commented out of its ``Block``, model/vit.py:133-134,140-141).  Not covered: the DeiT
+    distillation token / head, ``representation_size`` pre-logits and non-zero ``drop_rate`` / ``attn_drop_rate`` — the
+    constructor or the call says so instead of computing something else.
 
     ``precision``: 'fp32' (exact-fp32 MFMA, matches the CPU reference to ~1e-6), 'fp32x3' (fp32 operands split into bf16 hi + lo
     inside the GEMMs: the same results to a few 1e-6) or 'bf16' (bf16 MFMA operands with
     fp32 accumulation — the counterpart of the ``torch.cuda.amp.autocast()`` the reference wraps around
-    forward_features, utils/feature_extraction.py:35-36)."""
+    forward_features, utils/feature_extraction.py:35-36, and around the fine-tune forward, fine_tune_epoch.py:61)."""
 
     def __init__(self, volume_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, representation_size=None, distilled=False,
@@ -226,6 +296,7 @@ class VisionTransformer3D(nn.Module):
             del self.norm  # as the reference: fc_norm replaces norm (model/vit.py:218-221)
         self._precision = precision or 'fp32'
         self._encoder = None
+        self._trainer = None
         self.init_weights(weight_init)
 
     def init_weights(self, mode=''):
@@ -252,14 +323,22 @@ class VisionTransformer3D(nn.Module):
     def set_precision(self, precision: str):
         self._precision = precision
         self._encoder = None
+        self._trainer = None
+
+    def _encoder_params(self):
+        return [(n, p) for n, p in self.named_parameters() if not n.startswith('head.')]
 
     def forward_features(self, x):
         """[B, C, Lz, Hy, Wx] -> [B, embed_dim] (reference model/vit.py:265-284)."""
-        if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
-            raise VitaeError('VisionTransformer3D on MI355X is inference-only (feature extraction); call it under '
-                             'torch.no_grad() / model.eval() — fine-tuning is not built yet')
-        if (self.training and (self.drop_rate or self.attn_drop_rate or self.drop_path_rate)):
-            raise VitaeError('dropout / stochastic depth are not implemented; use model.eval()')
+        if self.training and (self.drop_rate or self.attn_drop_rate):
+            raise VitaeError('dropout is not implemented; use model.eval()')
+        if torch.is_grad_enabled() and self.training:
+            enc = self._encoder_params()
+            if any(p.requires_grad for _, p in enc):
+                if self._trainer is None:
+                    from ..encoder import HipEncoderTrainer
+                    self._trainer = HipEncoderTrainer(self, self._precision)
+                return _EncoderFunction.apply(self._trainer, tuple(n for n, _ in enc), x, *(p for _, p in enc))
         if self._encoder is None:
             from ..encoder import HipEncoder
             self._encoder = HipEncoder(self, self._precision)
@@ -269,6 +348,8 @@ class VisionTransformer3D(nn.Module):
         f = self.forward_features(x)
         if isinstance(self.head, nn.Identity):
             return f
+        if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
+            return _HeadFunction.apply(f, self.head.weight, self.head.bias, 0)
         return hip_linear(f, self.head.weight, self.head.bias)
 
 
