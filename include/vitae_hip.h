@@ -49,7 +49,8 @@ extern "C" {
 #define VITAE_HP_BETA1 1
 #define VITAE_HP_BETA2 2
 #define VITAE_HP_EPS 3
-#define VITAE_HP_BC1 4       /* 1 - beta1^t; <= 0: computed on the device from hp[VITAE_HP_STEP] (< 0: the slot holds -(1 - beta1)) */
+#define VITAE_HP_BC1 4       /* 1 - beta1^t; <= 0: computed on the device from hp[VITAE_HP_STEP] (< 0: the slot holds -(1 - beta1), which the
+                              * moment updates then use as their 1 - beta1 too instead of 1.f - fp32(beta1)) */
 #define VITAE_HP_BC2 5       /* 1 - beta2^t; same convention */
 #define VITAE_HP_GRAD_MUL 6  /* multiplier applied to grads inside AdamW (1/loss_scale; 1 here) */
 #define VITAE_HP_G_RECON 7   /* d total / d recon_loss  */

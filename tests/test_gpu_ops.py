@@ -899,6 +899,8 @@ def test_adamw_and_gradnorm(lib, C):
     p0, g1, g2 = gen(n, seed=1), gen(n, seed=2) * 0.01, gen(n, seed=3) * 0.01
     ref = p0.clone().requires_grad_(True)
     opt = torch.optim.AdamW([ref], lr=3e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.05)
+    ref64 = p0.double().requires_grad_(True)                    # the same steps in float64: what both fp32 results are measured against
+    opt64 = torch.optim.AdamW([ref64], lr=3e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.05)
     npad = (n + 3) // 4 * 4
     p, m, v = torch.zeros(npad, device='cuda'), torch.zeros(npad, device='cuda'), torch.zeros(npad, device='cuda')
     sh = torch.zeros(npad, dtype=torch.bfloat16, device='cuda')
@@ -909,6 +911,8 @@ def test_adamw_and_gradnorm(lib, C):
     for t, g in enumerate((g1, g2), 1):
         ref.grad = g.clone()
         opt.step()
+        ref64.grad = g.double()
+        opt64.step()
         gd = torch.zeros(npad, device='cuda'); gd[:n] = g.cuda()
         hp[C['VITAE_HP_LR']], hp[C['VITAE_HP_BETA1']], hp[C['VITAE_HP_BETA2']], hp[C['VITAE_HP_EPS']] = 3e-4, 0.9, 0.95, 1e-8
         hp[C['VITAE_HP_BC1']], hp[C['VITAE_HP_BC2']], hp[C['VITAE_HP_GRAD_MUL']] = 1 - 0.9 ** t, 1 - 0.95 ** t, 1.0
@@ -917,6 +921,11 @@ def test_adamw_and_gradnorm(lib, C):
         assert abs(float(gn) - float(g.norm())) < 1e-5 * float(g.norm())
         lib.vitae_adamw_step(p.data_ptr(), gd.data_ptr(), m.data_ptr(), v.data_ptr(), sh.data_ptr(), n, hp.data_ptr(), gn.data_ptr(), 0.05, st())
         assert rel_err(p[:n], ref) < 2e-6
+        # ... and as a share of the UPDATE (max|ref| above is 4.5: an update 3 % wrong would pass it): within 3 x the error torch's
+        # own fp32 AdamW makes against float64 on these inputs (tests/test_optimizer_kernels.py has the metric and the cases)
+        upd = float((ref64.detach() - p0.double()).norm())
+        e, e32 = float((p[:n].double().cpu() - ref64.detach()).norm()) / upd, float((ref.detach().double() - ref64.detach()).norm()) / upd
+        assert e <= 3.0 * e32, (t, e, e32)
         assert torch.equal(sh[:n], p[:n].to(torch.bfloat16))
     # non-finite gradient norm -> step skipped (GradScaler.step semantics)
     before = p.clone()
@@ -981,8 +990,10 @@ def test_adamw_bf16_moments(lib, C):
     lr, b1, b2, eps, wd = 3e-4, 0.9, 0.95, 1e-8, 0.05
     hp = torch.zeros(C['VITAE_HP_COUNT'], device='cuda')
     hp[C['VITAE_HP_LR']], hp[C['VITAE_HP_BETA1']], hp[C['VITAE_HP_BETA2']], hp[C['VITAE_HP_EPS']], hp[C['VITAE_HP_GRAD_MUL']] = lr, b1, b2, eps, 1.0
-    # the kernel's coefficients: 1 - beta formed in fp32 from the fp32 beta (with bf16 gradients many results sit next to a bf16 rounding
-    # boundary, and the 2e-7 between fp32(1 - beta) and 1 - fp32(beta) would flip a few per cent of them)
+    # the kernel's coefficients: with a bias-correction slot >= 0 (as here: host-computed corrections) 1 - beta is formed in fp32 from
+    # the fp32 beta (with bf16 gradients many results sit next to a bf16 rounding boundary, and the 2e-7 between fp32(1 - beta) and
+    # 1 - fp32(beta) would flip a few per cent of them).  With a NEGATIVE slot it is the slot's fp32(1 - beta):
+    # tests/test_optimizer_kernels.py runs the same emulation with those coefficients, at these tolerances.
     f32 = lambda x: torch.tensor(x, dtype=torch.float32)
     omb1, omb2, b2f = float(f32(1.0) - f32(b1)), float(f32(1.0) - f32(b2)), float(f32(b2))
     for g_bf16 in (False, True):

@@ -55,10 +55,31 @@ __global__ __launch_bounds__(64) void grad_norm_finalize_kernel(const double* __
 
 // 1 - beta^t on the device.  A NEGATIVE slot carries -(1 - beta) from the host's double (relative error 6e-8; fp32(0.999) itself is
 // 1.3e-8 off, which is 1.3e-5 of 1 - 0.999^t for small t): 1 - beta^t = -expm1(t log1p(-(1 - beta))).  Slot == 0: from fp32 beta.
-__device__ __forceinline__ void device_bias_corrections(float b1, float b2, float t, float& bc1, float& bc2) {
-    const float omb1 = bc1 < 0.f ? -bc1 : 1.f - b1, omb2 = bc2 < 0.f ? -bc2 : 1.f - b2;
-    bc1 = -expm1f(t * log1pf(-omb1));
-    bc2 = -expm1f(t * log1pf(-omb2));
+__device__ __forceinline__ void device_bias_corrections(float omb1, float omb2, float t, float& bc1, float& bc2) {
+    // the products are rounded HERE in every instantiation: the empty asm keeps them out of a fused multiply-add at the top of expm1f
+    float x1 = t * log1pf(-omb1), x2 = t * log1pf(-omb2);
+    asm volatile("" : "+v"(x1), "+v"(x2));
+    bc1 = -expm1f(x1);
+    bc2 = -expm1f(x2);
+}
+
+// 1 - beta as the moment updates and the bias corrections use it: the host's double-formed value when the slot carries it (negative
+// slot), else 1.f - fp32(beta).  The latter is 4.7e-5 off 1 - 0.999 (fp32(0.999) is 1.3e-8 off, all of which lands in the difference)
+// and so is every (1 - beta2) g^2 formed from it: 2.4-6.4 times the error of a plain fp32 AdamW at beta2 = 0.999, none at 0.95.
+__device__ __forceinline__ float one_minus_beta(float slot, float b) { return slot < 0.f ? -slot : 1.f - b; }
+
+// One element of the step with every fused multiply-add spelled out.  The library is built with -ffp-contract=fast, and where a sum has
+// two products (b2 v + (1 - b2) g^2; g gs - m; 1 - lr wd) the compiler is free to fuse either one.  In the scalar tail of adamw_kernel it
+// chose differently for fp32 and for bf16 gradients: v of a tail element differed in the last bit between vitae_adamw_step and
+// vitae_adamw_step_bf16g on the same values once v was not zero (tests/test_optimizer_kernels.py).  Written this way the gradient and
+// moment types, the unrolled groups, the scalar tail and vitae_opt_tail all round alike, and GRAD_MUL = 2^-k on gradients x 2^k is exact.
+__device__ __forceinline__ float adamw_decay(float lr, float weight_decay) { return __builtin_fmaf(-lr, weight_decay, 1.0f); }
+__device__ __forceinline__ void adamw_element(float& p, float& m, float& v, float g, float gs, float decay, float omb1, float b2, float omb2,
+                                              float step, float sq_bc2, float eps) {
+    m = __builtin_fmaf(omb1, __builtin_fmaf(g, gs, -m), m);              // exp_avg.lerp_(grad, 1 - beta1)
+    const float ge = g * gs;
+    v = __builtin_fmaf(b2, v, omb2 * ge * ge);
+    p = __builtin_fmaf(-step, m / (sqrtf(v) / sq_bc2 + eps), p * decay);
 }
 
 // The moments are stored either as fp32 or as bf16 (round 6: `S`).  bf16 moments: the step is COMPUTED in fp32 from the stored
@@ -105,13 +126,14 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
     const float lr = hp[VITAE_HP_LR], b1 = hp[VITAE_HP_BETA1], b2 = hp[VITAE_HP_BETA2], eps = hp[VITAE_HP_EPS];
     float bc1 = hp[VITAE_HP_BC1], bc2 = hp[VITAE_HP_BC2];
+    const float omb1 = one_minus_beta(bc1, b1), omb2 = one_minus_beta(bc2, b2);
     if (bc1 <= 0.f) {            // the host left the bias corrections to the device: t = applied steps + 1 (vitae_hip.h VITAE_HP_STEP)
         const float t = hp[VITAE_HP_STEP] + 1.f;
-        device_bias_corrections(b1, b2, t, bc1, bc2);
+        device_bias_corrections(omb1, omb2, t, bc1, bc2);
     }
     const float sq_bc2 = sqrtf(bc2);
     const float gs = hp[VITAE_HP_GRAD_MUL];
-    const float decay = 1.0f - lr * weight_decay, step = lr / bc1;
+    const float decay = adamw_decay(lr, weight_decay), step = lr / bc1;
     const long n4 = n / 4;
     f32x4* p4 = reinterpret_cast<f32x4*>(p);
     // two independent 16-byte groups per thread and iteration: 8 loads in flight before the first dependent use.
@@ -139,11 +161,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
             const long i = idx[u];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float ge = gg[u][e] * gs;
-                pp[u][e] *= decay;
-                mm[u][e] = mm[u][e] + (1.f - b1) * (ge - mm[u][e]);   // exp_avg.lerp_(grad, 1 - beta1)
-                vv[u][e] = b2 * vv[u][e] + (1.f - b2) * ge * ge;
-                pp[u][e] -= step * (mm[u][e] / (sqrtf(vv[u][e]) / sq_bc2 + eps));
+                float pe = pp[u][e], me = mm[u][e], ve = vv[u][e];
+                adamw_element(pe, me, ve, gg[u][e], gs, decay, omb1, b2, omb2, step, sq_bc2, eps);
+                pp[u][e] = pe; mm[u][e] = me; vv[u][e] = ve;
             }
             p4[i] = pp[u];
             state4_st<S>(m, i, mm[u]);
@@ -158,12 +178,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
     if (blockIdx.x == 0) {
         for (long i = n4 * 4 + threadIdx.x; i < n; i += 256) {
-            const float gg = (float)g[i] * gs;
-            float pp = p[i] * decay;
-            const float mo = (float)m[i];
-            const float mm = mo + (1.f - b1) * (gg - mo);
-            const float vv = b2 * (float)v[i] + (1.f - b2) * gg * gg;
-            pp -= step * (mm / (sqrtf(vv) / sq_bc2 + eps));
+            float pp = p[i], mm = (float)m[i], vv = (float)v[i];
+            adamw_element(pp, mm, vv, (float)g[i], gs, decay, omb1, b2, omb2, step, sq_bc2, eps);
             p[i] = pp; m[i] = (S)mm; v[i] = (S)vv;
             if (shadow) shadow[i] = (__bf16)pp;
         }
@@ -216,23 +232,22 @@ __global__ __launch_bounds__(256) void opt_tail_adamw_kernel(float* __restrict__
     if (finite) {
         const float lr = hp[VITAE_HP_LR], b1 = hp[VITAE_HP_BETA1], b2 = hp[VITAE_HP_BETA2], eps = hp[VITAE_HP_EPS];
         float bc1 = hp[VITAE_HP_BC1], bc2 = hp[VITAE_HP_BC2];
+        const float omb1 = one_minus_beta(bc1, b1), omb2 = one_minus_beta(bc2, b2);
         if (bc1 <= 0.f) {
             const float t = hp[VITAE_HP_STEP] + 1.f;
-            device_bias_corrections(b1, b2, t, bc1, bc2);
+            device_bias_corrections(omb1, omb2, t, bc1, bc2);
         }
         const float sq_bc2 = sqrtf(bc2), gs = hp[VITAE_HP_GRAD_MUL], step = lr / bc1;
         const long n = n_decay + n_plain;                  // both segment lengths are multiples of 4 (arena alignment)
         for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) {
-            const float decay = 1.0f - lr * (i < n_decay ? weight_decay : 0.f);
+            const float decay = adamw_decay(lr, i < n_decay ? weight_decay : 0.f);
             f32x4 pp = *reinterpret_cast<f32x4*>(p + i), mm = state4_ld<S>(m, i / 4), vv = state4_ld<S>(v, i / 4);
             const f32x4 gg = grad4<G>(g, i / 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float ge = gg[e] * gs;
-                pp[e] *= decay;
-                mm[e] = mm[e] + (1.f - b1) * (ge - mm[e]);
-                vv[e] = b2 * vv[e] + (1.f - b2) * ge * ge;
-                pp[e] -= step * (mm[e] / (sqrtf(vv[e]) / sq_bc2 + eps));
+                float pe = pp[e], me = mm[e], ve = vv[e];
+                adamw_element(pe, me, ve, gg[e], gs, decay, omb1, b2, omb2, step, sq_bc2, eps);
+                pp[e] = pe; mm[e] = me; vv[e] = ve;
             }
             *reinterpret_cast<f32x4*>(p + i) = pp;
             state4_st<S>(m, i / 4, mm);
