@@ -240,7 +240,9 @@ int vitae_layernorm_bwd(const float* dy, const float* x, const float* w, const f
 /* The same without atomics (round 4): a launch of vitae_layernorm_bwd_part_records(M) workgroups, each leaving its column partials
  * [d gamma | d beta | colsum(dx)] as one 3 D-float record in part[records][3][D]; vitae_ln_grad_reduce adds the records of n
  * LayerNorm instances (HOST arrays of pointers / counts; dx_colsum entries may be NULL) into dw / db / dx_colsum in ONE launch,
- * in a fixed order (bitwise reproducible).  D in {256, 512, 768, 1024}, 16-byte aligned operands. */
+ * in a fixed order (bitwise reproducible).  D in {256, 512, 768, 1024}, 16-byte aligned operands.  vitae_ln_grad_reduce itself
+ * takes any D % 4 == 0 and moves float4 groups: every non-NULL part / dw / db / dx_colsum pointer of every instance must be 16-byte
+ * aligned, else VITAE_ERR_UNSUPPORTED_SHAPE; the whole call is judged before its first launch (nothing is written on an error). */
 int vitae_layernorm_bwd_part_records(int M);
 int vitae_layernorm_bwd_part(const float* dy, const float* x, const float* w, const float* mean, const float* rstd,
                              float* dx, float* part, void* dx_bf16, int M, int D, int dx_accumulate, void* stream);
@@ -423,7 +425,8 @@ int vitae_loss_finalize(const double* acc, const float* hp, float* out4, float m
 
 /* ---- contrastive head ----------------------------------------------------------------------------
  * BatchNorm1d (training) + ReLU of the predictor (model/vit_autoenc.py:263-268); running stats updated
- * in place (momentum 0.1, unbiased variance). */
+ * in place (momentum as given, unbiased variance).  running_mean == NULL: no running statistics — running_var and
+ * num_batches_tracked are left untouched as well. */
 int vitae_bn1d_relu_fwd(const float* x, const float* w, const float* b, float* y, void* y_bf16 /* optional bf16 copy of y: the next
                         Linear's GEMM operand */, float* save_mean, float* save_rstd,
                         float* running_mean, float* running_var, long long* num_batches_tracked, int R, int D,

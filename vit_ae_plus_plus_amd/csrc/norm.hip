@@ -13,6 +13,22 @@ namespace {
 
 constexpr int LN_MAX_PER_LANE = 16;   // D <= 1024
 
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The row mean from a DOUBLE sum, as two floats: mean0 = fp32(mean), corr = fp32(mean - mean0).  An fp32 sum leaves the mean a few ulp
+// of sum |x| / D off: 1e-4 of a deviation for a row of mean 1000 and deviation 1 (all of it went into y: 21 x the plain fp32
+// statement), and where |mean| << deviation an ulp of the mean itself, which a one-row d(gamma) = dy (x - mean) rstd shows in full
+// (3.1 - 3.7 x).  One float cannot hold a mean of 1000 to better than 3e-5 either: x - mean is formed as (x - mean0) - corr.
+__device__ __forceinline__ void ln_mean2(double lane_sum, int D, float& mean0, float& corr) {
+    const double m = wave_sum_f64(lane_sum) / (double)D;
+    mean0 = (float)m;
+    corr = (float)(m - (double)mean0);
+}
+
 // ------------------------------------------------------------------ LayerNorm forward
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ b, float* __restrict__ y,
@@ -24,27 +40,29 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     const int lane = threadIdx.x & 63;
     const float* xr = x + (long)row * D;
     float v[LN_MAX_PER_LANE];
-    float s = 0.f;
+    double s = 0.;
 #pragma unroll
     for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
         const int c = lane + 64 * i;
         v[i] = c < D ? xr[c] : 0.f;
-        s += v[i];
+        s += (double)v[i];
     }
-    const float mean = wave_sum(s) / D;
+    float mean0, corr;
+    ln_mean2(s, D, mean0, corr);
+    const float mean = mean0 + corr;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
         const int c = lane + 64 * i;
-        const float d = c < D ? v[i] - mean : 0.f;
-        q += d * d;
+        v[i] = c < D ? (v[i] - mean0) - corr : 0.f;
+        q += v[i] * v[i];
     }
     const float rstd = rsqrtf(wave_sum(q) / D + eps);
 #pragma unroll
     for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
         const int c = lane + 64 * i;
         if (c < D) {
-            const float o = (v[i] - mean) * rstd * w[c] + b[c];
+            const float o = v[i] * rstd * w[c] + b[c];
             if (y) y[(long)row * D + c] = o;
             if (y16) y16[(long)row * D + c] = (__bf16)o;
         }
@@ -68,24 +86,26 @@ __global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const float* __r
     const f32x4* w4 = reinterpret_cast<const f32x4*>(w);
     const f32x4* b4 = reinterpret_cast<const f32x4*>(b);
     f32x4 v[NV], wv[NV], bv[NV];
-    float s = 0.f;
+    double s = 0.;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         v[i] = xr[lane + 64 * i]; wv[i] = w4[lane + 64 * i]; bv[i] = b4[lane + 64 * i];
-        s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+        s += ((double)v[i][0] + (double)v[i][1]) + ((double)v[i][2] + (double)v[i][3]);
     }
-    const float mean = wave_sum(s) / D;
+    float mean0, corr;
+    ln_mean2(s, D, mean0, corr);
+    const float mean = mean0 + corr;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; q += d * d; }
+        for (int e = 0; e < 4; ++e) { v[i][e] = (v[i][e] - mean0) - corr; q += v[i][e] * v[i][e]; }
     const float rstd = rsqrtf(wave_sum(q) / D + eps);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mean) * rstd * wv[i][e] + bv[i][e];
+        for (int e = 0; e < 4; ++e) o[e] = v[i][e] * rstd * wv[i][e] + bv[i][e];
         if (y) reinterpret_cast<f32x4*>(y + (long)row * D)[lane + 64 * i] = o;
         if (y16) {
             bf16x4 o16;
@@ -507,6 +527,41 @@ __device__ __forceinline__ f32x4 bn_col_reduce4(f32x4 v, f32x4 (*red)[BN_CG], in
     return s;
 }
 
+// The column mean from per-thread DOUBLE sums, returned as two floats: mean0 = fp32(mean), corr = fp32(mean - mean0).  An fp32 sum
+// leaves the mean a few ulp of sum |x| off — 4e-7 of the running-mean update where |mean| << deviation, 1e-4 of a deviation where
+// |mean| = 1000 deviations — and one float cannot hold a mean of 1000 to better than 3e-5; x - mean is formed as (x - mean0) - corr.
+__device__ __forceinline__ void bn_col_sum_f64(const double (&s)[4], double (*redd)[BN_CG][4], int cg, int rg, double (&out)[4]) {
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) redd[rg][cg][e] = s[e];
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        double t = redd[0][cg][e];
+#pragma unroll
+        for (int g = 1; g < BN_RG; ++g) t += redd[g][cg][e];
+        out[e] = t;
+    }
+}
+
+__device__ __forceinline__ void bn_col_mean2(const double (&s)[4], double (*redd)[BN_CG][4], int cg, int rg, float n, f32x4& mean0, f32x4& corr) {
+    double t[4];
+    bn_col_sum_f64(s, redd, cg, rg, t);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const double m = t[e] / (double)n;
+        mean0[e] = (float)m;
+        corr[e] = (float)(m - (double)mean0[e]);
+    }
+}
+
+// M2 is summed in double as well: y = xhat w + b can cancel (w = 0.05, b = -0.07: a column whose largest output is a quarter of
+// xhat w), and an fp32 M2 1e-7 off then showed as 6e-7 of that column's y, 3 x the plain fp32 statement
+__device__ __forceinline__ void bn_sq_acc(double (&q)[4], const f32x4 d) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q[e] += (double)d[e] * (double)d[e];
+}
+
 __global__ __launch_bounds__(256) void bn1d_relu_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ b, float* __restrict__ y, __bf16* __restrict__ y16,
                                                             float* __restrict__ save_mean, float* __restrict__ save_rstd,
@@ -519,19 +574,8 @@ __global__ __launch_bounds__(256) void bn1d_relu_fwd_kernel(const float* __restr
     const int c = blockIdx.x * BN_COLS + 4 * cg;
     const bool ok = c < D;                                  // D % 4 == 0 (launcher)
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    f32x4 s = z;
-    if (ok) {
-        int r = rg;
-        for (; r + 3 * BN_RG < R; r += 4 * BN_RG) {
-            f32x4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(x + (long)(r + u * BN_RG) * D + c);
-            s += (v[0] + v[1]) + (v[2] + v[3]);
-        }
-        for (; r < R; r += BN_RG) s += *reinterpret_cast<const f32x4*>(x + (long)r * D + c);
-    }
-    const f32x4 mean = bn_col_reduce4(s, red, cg, rg) / (float)R;
-    f32x4 q = z;
+    __shared__ double redd[BN_RG][BN_CG][4];
+    double s[4] = {0., 0., 0., 0.};
     if (ok) {
         int r = rg;
         for (; r + 3 * BN_RG < R; r += 4 * BN_RG) {
@@ -539,19 +583,40 @@ __global__ __launch_bounds__(256) void bn1d_relu_fwd_kernel(const float* __restr
 #pragma unroll
             for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(x + (long)(r + u * BN_RG) * D + c);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { const f32x4 d = v[u] - mean; q += d * d; }
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s[e] += (double)v[u][e];
         }
-        for (; r < R; r += BN_RG) { const f32x4 d = *reinterpret_cast<const f32x4*>(x + (long)r * D + c) - mean; q += d * d; }
+        for (; r < R; r += BN_RG) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(x + (long)r * D + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] += (double)v[e];
+        }
     }
-    q = bn_col_reduce4(q, red, cg, rg);
+    f32x4 mean0, corr;
+    bn_col_mean2(s, redd, cg, rg, (float)R, mean0, corr);
+    double q[4] = {0., 0., 0., 0.};
+    if (ok) {
+        int r = rg;
+        for (; r + 3 * BN_RG < R; r += 4 * BN_RG) {
+            f32x4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(x + (long)(r + u * BN_RG) * D + c);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) bn_sq_acc(q, (v[u] - mean0) - corr);
+        }
+        for (; r < R; r += BN_RG) bn_sq_acc(q, (*reinterpret_cast<const f32x4*>(x + (long)r * D + c) - mean0) - corr);
+    }
+    bn_col_sum_f64(q, redd, cg, rg, q);
     if (!ok) return;
+    const f32x4 mean = mean0 + corr;
     f32x4 rstd;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) rstd[e] = rsqrtf(q[e] / R + eps);
+    for (int e = 0; e < 4; ++e) rstd[e] = (float)(1. / sqrt(q[e] / R + (double)eps));
     const f32x4 g = *reinterpret_cast<const f32x4*>(w + c), be = *reinterpret_cast<const f32x4*>(b + c);
     const f32x4 sc = rstd * g;
     for (int r = rg; r < R; r += BN_RG) {
-        f32x4 v = (*reinterpret_cast<const f32x4*>(x + (long)r * D + c) - mean) * sc + be;
+        f32x4 v = ((*reinterpret_cast<const f32x4*>(x + (long)r * D + c) - mean0) - corr) * sc + be;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
         *reinterpret_cast<f32x4*>(y + (long)r * D + c) = v;
@@ -568,8 +633,9 @@ __global__ __launch_bounds__(256) void bn1d_relu_fwd_kernel(const float* __restr
         if (run_mean) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                run_mean[c + e] = (1.f - momentum) * run_mean[c + e] + momentum * mean[e];
-                run_var[c + e] = (1.f - momentum) * run_var[c + e] + momentum * (q[e] / (R > 1 ? R - 1 : 1));
+                // (in double, rounded once: five fp32 roundings lined up to 2.9e-7 of the update in one column of a test)
+                run_mean[c + e] = (float)((1. - (double)momentum) * (double)run_mean[c + e] + (double)momentum * ((double)mean0[e] + (double)corr[e]));
+                run_var[c + e] = (float)((1. - (double)momentum) * (double)run_var[c + e] + (double)momentum * (q[e] / (R > 1 ? R - 1 : 1)));
             }
         }
     }
@@ -660,7 +726,7 @@ __global__ __launch_bounds__(256) void bn1d_relu_bwd_kernel(const float* __restr
 // The kernels above give a 64-column strip ALL R rows: D / 64 = 12 workgroups for the predictor (D = 768) whatever R is — 12 of
 // 256 CUs stream 1760 rows at batch 32 / patch 8 (45 us forward, 78 us backward per view, 0.36 TB/s).  Here a launch is
 // (D / 64) x RS workgroups, and an op is two launches with RS partial records per column in between:
-//   forward:  (1) per split, the local mean and the local sum of squared deviations (two passes over rows that stay in L2);
+//   forward:  (1) per split, the local mean (as two floats) and the local sum of squared deviations (two passes over rows that stay in L2);
 //             (2) every workgroup merges the RS records in split order with Chan's update (mean = sum n_i mean_i / R,
 //                 M2 = sum M2_i + n_i (mean_i - mean)^2 — no E[x^2] - E[x]^2 cancellation), then normalises its own rows;
 //   backward: (1) per split, sum(g) and sum(g xhat) (g = dy where y > 0); (2) the sums of all splits in order, then dx of its rows.
@@ -679,17 +745,31 @@ __global__ __launch_bounds__(256) void bn1d_stats_part_kernel(const float* __res
     int r0, r1;
     bn_split_rows(sp, R, r0, r1);
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    f32x4 s = z;
+    // a split's record is [mean0 | corr | M2]: its mean as TWO floats (bn_col_mean2) — rounded to one float, a split mean of 1000
+    // is 3e-5 off, and the merge's n_i (mean_i - mean)^2 took that as 2e-5 of save_rstd for a column of mean 1000 and deviation 1
+    // (200 x the one-workgroup form)
+    __shared__ double redd[BN_RG][BN_CG][4];
+    const float n = (float)max(r1 - r0, 1);
+    double s[4] = {0., 0., 0., 0.};
     if (ok)
-        for (int r = r0 + rg; r < r1; r += BN_RG) s += *reinterpret_cast<const f32x4*>(x + (long)r * D + c);
-    const f32x4 mean = bn_col_reduce4(s, red, cg, rg) / (float)max(r1 - r0, 1);
-    f32x4 q = z;
+        for (int r = r0 + rg; r < r1; r += BN_RG) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(x + (long)r * D + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] += (double)v[e];
+        }
+    f32x4 mean0, corr;
+    bn_col_mean2(s, redd, cg, rg, n, mean0, corr);
+    double qd[4] = {0., 0., 0., 0.};
     if (ok)
-        for (int r = r0 + rg; r < r1; r += BN_RG) { const f32x4 d = *reinterpret_cast<const f32x4*>(x + (long)r * D + c) - mean; q += d * d; }
-    q = bn_col_reduce4(q, red, cg, rg);
+        for (int r = r0 + rg; r < r1; r += BN_RG) bn_sq_acc(qd, (*reinterpret_cast<const f32x4*>(x + (long)r * D + c) - mean0) - corr);
+    bn_col_sum_f64(qd, redd, cg, rg, qd);
+    f32x4 q;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q[e] = (float)qd[e];
     if (ok && rg == 0) {
-        *reinterpret_cast<f32x4*>(part + ((long)blockIdx.y * 2 + 0) * D + c) = mean;
-        *reinterpret_cast<f32x4*>(part + ((long)blockIdx.y * 2 + 1) * D + c) = q;
+        *reinterpret_cast<f32x4*>(part + ((long)blockIdx.y * 3 + 0) * D + c) = mean0;
+        *reinterpret_cast<f32x4*>(part + ((long)blockIdx.y * 3 + 1) * D + c) = corr;
+        *reinterpret_cast<f32x4*>(part + ((long)blockIdx.y * 3 + 2) * D + c) = q;
     }
 }
 
@@ -704,27 +784,37 @@ __global__ __launch_bounds__(256) void bn1d_relu_apply_part_kernel(const float* 
     const int c = blockIdx.x * BN_COLS + 4 * cg;
     if (c >= D) return;
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    f32x4 mean = z;
+    double md[4] = {0., 0., 0., 0.};                                  // the merged mean in double, then again as two floats
     for (int i = 0; i < sp.RS; ++i) {
-        const float n = (float)(min(R, (i + 1) * sp.rps) - i * sp.rps);
-        mean += n * *reinterpret_cast<const f32x4*>(part + ((long)i * 2 + 0) * D + c);
+        const double n = (double)(min(R, (i + 1) * sp.rps) - i * sp.rps);
+        const f32x4 m0 = *reinterpret_cast<const f32x4*>(part + ((long)i * 3 + 0) * D + c), m1 = *reinterpret_cast<const f32x4*>(part + ((long)i * 3 + 1) * D + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) md[e] += n * ((double)m0[e] + (double)m1[e]);
     }
-    mean = mean / (float)R;
-    f32x4 q = z;
+    f32x4 mean0, corr;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { md[e] /= (double)R; mean0[e] = (float)md[e]; corr[e] = (float)(md[e] - (double)mean0[e]); }
+    const f32x4 mean = mean0 + corr;
+    double q[4] = {0., 0., 0., 0.};
     for (int i = 0; i < sp.RS; ++i) {
-        const float n = (float)(min(R, (i + 1) * sp.rps) - i * sp.rps);
-        const f32x4 d = *reinterpret_cast<const f32x4*>(part + ((long)i * 2 + 0) * D + c) - mean;
-        q += *reinterpret_cast<const f32x4*>(part + ((long)i * 2 + 1) * D + c) + n * (d * d);
+        const double n = (double)(min(R, (i + 1) * sp.rps) - i * sp.rps);
+        const f32x4 m0 = *reinterpret_cast<const f32x4*>(part + ((long)i * 3 + 0) * D + c), m1 = *reinterpret_cast<const f32x4*>(part + ((long)i * 3 + 1) * D + c);
+        const f32x4 m2 = *reinterpret_cast<const f32x4*>(part + ((long)i * 3 + 2) * D + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double d = ((double)m0[e] + (double)m1[e]) - md[e];
+            q[e] += (double)m2[e] + n * (d * d);
+        }
     }
     f32x4 rstd;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) rstd[e] = rsqrtf(q[e] / R + eps);
+    for (int e = 0; e < 4; ++e) rstd[e] = (float)(1. / sqrt(q[e] / R + (double)eps));
     const f32x4 g = *reinterpret_cast<const f32x4*>(w + c), be = *reinterpret_cast<const f32x4*>(b + c);
     const f32x4 sc = rstd * g;
     int r0, r1;
     bn_split_rows(sp, R, r0, r1);
     for (int r = r0 + rg; r < r1; r += BN_RG) {
-        f32x4 v = (*reinterpret_cast<const f32x4*>(x + (long)r * D + c) - mean) * sc + be;
+        f32x4 v = ((*reinterpret_cast<const f32x4*>(x + (long)r * D + c) - mean0) - corr) * sc + be;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
         *reinterpret_cast<f32x4*>(y + (long)r * D + c) = v;
@@ -741,8 +831,9 @@ __global__ __launch_bounds__(256) void bn1d_relu_apply_part_kernel(const float* 
         if (run_mean) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                run_mean[c + e] = (1.f - momentum) * run_mean[c + e] + momentum * mean[e];
-                run_var[c + e] = (1.f - momentum) * run_var[c + e] + momentum * (q[e] / (R > 1 ? R - 1 : 1));
+                // (in double, rounded once: five fp32 roundings lined up to 2.9e-7 of the update in one column of a test)
+                run_mean[c + e] = (float)((1. - (double)momentum) * (double)run_mean[c + e] + (double)momentum * ((double)mean0[e] + (double)corr[e]));
+                run_var[c + e] = (float)((1. - (double)momentum) * (double)run_var[c + e] + (double)momentum * (q[e] / (R > 1 ? R - 1 : 1)));
             }
         }
     }
@@ -908,12 +999,18 @@ extern "C" int vitae_layernorm_bwd_part(const float* dy, const float* x, const f
 extern "C" int vitae_ln_grad_reduce(int n, const float* const* part, float* const* dw, float* const* db, float* const* dx_colsum,
                                     const int* records, const int* D, void* stream) {
     if (n <= 0 || !part || !dw || !db || !records || !D) return VITAE_ERR_INVALID_ARG;
+    // the whole call is judged before its first launch: the kernel moves float4 groups of part and read-modify-writes float4 groups
+    // of dw / db / dx_colsum, so every non-NULL pointer of every instance has to be 16-byte aligned
+    for (int i = 0; i < n; ++i) {
+        if (!part[i] || records[i] <= 0 || D[i] <= 0 || (D[i] & 3)) return VITAE_ERR_INVALID_ARG;
+        if (((uintptr_t)part[i] | (uintptr_t)dw[i] | (uintptr_t)db[i] | (uintptr_t)(dx_colsum ? dx_colsum[i] : nullptr)) & 15)
+            return VITAE_ERR_UNSUPPORTED_SHAPE;
+    }
     for (int i0 = 0; i0 < n; i0 += LN_RED_MAX) {
         LnRedArgs a;
         const int m = n - i0 < LN_RED_MAX ? n - i0 : LN_RED_MAX;
         int dmax = 0;
         for (int i = 0; i < m; ++i) {
-            if (!part[i0 + i] || records[i0 + i] <= 0 || (D[i0 + i] & 3)) return VITAE_ERR_INVALID_ARG;
             a.d[i] = LnRedDesc{part[i0 + i], dw[i0 + i], db[i0 + i], dx_colsum ? dx_colsum[i0 + i] : nullptr, records[i0 + i], D[i0 + i]};
             if (D[i0 + i] > dmax) dmax = D[i0 + i];
         }
@@ -942,6 +1039,7 @@ extern "C" int vitae_bn1d_relu_fwd(const float* x, const float* w, const float* 
                                    void* stream) {
     if (!x || !w || !b || !y || !save_mean || !save_rstd || R <= 0 || D <= 0) return VITAE_ERR_INVALID_ARG;
     if (!bn_vec_ok(D, {x, w, b, y, save_mean, save_rstd}) || ((uintptr_t)y_bf16 & 7)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (!running_mean) num_batches_tracked = nullptr;      // no running statistics: the step is not counted either
     hipLaunchKernelGGL(bn1d_relu_fwd_kernel, dim3(cdiv(D, BN_COLS)), dim3(256), 0, (hipStream_t)stream, x, w, b, y,
                        reinterpret_cast<__bf16*>(y_bf16), save_mean, save_rstd, running_mean, running_var, num_batches_tracked, R, D, eps, momentum);
     return vitae_launch_status();
@@ -971,7 +1069,7 @@ extern "C" int vitae_bn1d_relu_bwd(const float* dy, const float* x, const float*
 // ws: vitae_bn1d_split_ws_floats(R, D) floats, used between the two launches of a call only.
 extern "C" long vitae_bn1d_split_ws_floats(int R, int D) {
     if (R <= 0 || D <= 0) return 0;
-    return (long)bn_split_plan(R, D).RS * 2 * D;
+    return (long)bn_split_plan(R, D).RS * 3 * D;      // the forward's records are three floats a column, the backward's two
 }
 
 extern "C" int vitae_bn1d_relu_fwd_split(const float* x, const float* w, const float* b, float* y, void* y_bf16, float* save_mean,
@@ -979,6 +1077,7 @@ extern "C" int vitae_bn1d_relu_fwd_split(const float* x, const float* w, const f
                                          int R, int D, float eps, float momentum, float* ws, void* stream) {
     if (!x || !w || !b || !y || !save_mean || !save_rstd || !ws || R <= 0 || D <= 0) return VITAE_ERR_INVALID_ARG;
     if (!bn_vec_ok(D, {x, w, b, y, save_mean, save_rstd, ws}) || ((uintptr_t)y_bf16 & 7)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (!running_mean) num_batches_tracked = nullptr;
     const BnSplit sp = bn_split_plan(R, D);
     const dim3 grid(cdiv(D, BN_COLS), sp.RS);
     hipLaunchKernelGGL(bn1d_stats_part_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, ws, R, D, sp);
