@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define VITAE_ABI_VERSION 49
+#define VITAE_ABI_VERSION 50
 
 /* matrix-core arithmetic of the dense contractions */
 #define VITAE_PREC_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32 (the reference's precision, autocast off at utils/train_one_epoch.py:50) */
@@ -313,6 +313,38 @@ int vitae_decoder_assemble_fwd(const float* e, const float* mask_token, const fl
  * LDS-DMA GEMM); dmask_token_accum[Dd] += sum of dxd over the masked positions.  One launch. */
 int vitae_decoder_assemble_bwd(const float* dxd, const int* ids_shuffle, float* de, void* de_bf16, float* dmask_token_accum,
                                int B, int L, int keep, int Dd, void* stream);
+
+/* ---- classifier end of fine-tuning (post_training_utils/fine_tune_epoch.py:58-63,104-145,366-376; ABI 50) ----------------------
+ * vitae_cls_loss: class-weighted cross entropy of logits[B, C] (fp32, row stride ld >= C) in ONE launch.  Exactly one of
+ *   labels (HARD mode: int64 [B], torch.nn.CrossEntropyLoss(weight = w), mean reduction) and targets (SOFT mode: fp32 [B, C]
+ *   contiguous, utils/custom_loss.py:12-18) is given; w [C] may be NULL (all ones).  With p = softmax(logits[n]), logp = its log
+ *   (row maximum subtracted):
+ *     hard: loss = sum_n w[y_n] (-logp[n, y_n]) / sum_n w[y_n];  dlogits[n, c] = g w[y_n] (p[n, c] - [c == y_n]) / sum_m w[y_m].
+ *           Rows with label -100 (ignore_index) contribute nothing and get a zero gradient; when every row is ignored the loss
+ *           is NaN, as torch gives.  Any other label outside [0, C) is an argument error that cannot be seen without reading
+ *           the labels back: the LOSS becomes NaN instead, the row gets a zero gradient and is left out of `confusion`, and
+ *           nothing is read or written out of range.
+ *     soft: loss = sum_n sum_c -t[n, c] w[c] logp[n, c] / (C sum_c w[c]);
+ *           dlogits[n, k] = g (p[n, k] sum_c t[n, c] w[c] - t[n, k] w[k]) / (C sum_c w[c]).
+ *   Outputs (device pointers; each optional except loss; none may overlap an input): loss (one float), dlogits [B, C] (already
+ *   scaled by the upstream gradient g: the g = 1 value rounded to fp32, times g), probs [B, C] (the softmax), pred [B] (int32
+ *   argmax, a tie goes to the lowest index as torch.max), confusion [C * C] (int32, hard mode only, ADDED to: cell
+ *   pred * C + label — sklearn's confusion_matrix(predictions, target) as utils/used_metrics.py:34-39 reads it).
+ *   Everything between the fp32 inputs and the fp32 outputs is evaluated in double in a fixed order (one workgroup, no float
+ *   atomics): bitwise reproducible.  1 <= C <= 1024 (more: VITAE_ERR_UNSUPPORTED_SHAPE), any B >= 1.
+ * vitae_mixup_pairs: batch-mode Mixup of x[B, n] (fp32): x[i] <- lam x[i] + (1 - lam) x[B-1-i] for every i at once, in place
+ *   (dst NULL or == x) or into dst (no partial overlap).  Samples i and B-1-i are read and written together: one read and one
+ *   write of the batch.  The middle sample of an odd B, and every sample when lam == 1, come out bit for bit.  Evaluated in
+ *   double from the double lam and rounded once.  16-byte accesses when x, dst and n allow, scalar ones otherwise: any n >= 1,
+ *   B >= 1 and 4-byte aligned pointer is served.  0 <= lam <= 1.
+ * vitae_mixup_targets: out[B, C] (fp32) = lam oh(y) + (1 - lam) oh(flip(y)) with the label-smoothed one-hot rows oh(y)[c] =
+ *   c == y ? 1 - smoothing + smoothing / C : smoothing / C; labels int64 [B].  A label outside [0, C) is an argument error
+ *   that cannot be seen without reading the labels back: every row that depends on it (row i and row B-1-i) is filled with
+ *   NaN instead, the other rows are right. */
+int vitae_cls_loss(const float* logits, long ld, const long long* labels, const float* targets, const float* w, float g,
+                   float* loss, float* dlogits, float* probs, int* pred, int* confusion, int B, int C, void* stream);
+int vitae_mixup_pairs(float* x, float* dst, double lam, int B, long n, void* stream);
+int vitae_mixup_targets(const long long* labels, float* out, double lam, double smoothing, int B, int C, void* stream);
 
 /* ---- perceptual-loss hook, forward only (model/model_utils/perceptual_loss.py:46-77; a no-gradient logging term,
  * model/vit_autoenc.py:229-230).  VGG16's convolutions run as vitae_gemm_glds (bias + VITAE_EPI_RELU) over im2col matrices in

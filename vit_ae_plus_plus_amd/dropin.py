@@ -24,6 +24,8 @@ _ALIASES = {
     'utils.train_one_epoch': 'vit_ae_plus_plus_amd.utils.train_one_epoch',
     'utils.custom_loss': 'vit_ae_plus_plus_amd.utils.custom_loss',
     'utils.lr_decay': 'vit_ae_plus_plus_amd.utils.lr_decay',
+    'utils.used_metrics': 'vit_ae_plus_plus_amd.utils.used_metrics',
+    'utils.mixup': 'vit_ae_plus_plus_amd.utils.mixup',
     'post_training_utils': 'vit_ae_plus_plus_amd.post_training_utils',
     'post_training_utils.fine_tune_epoch': 'vit_ae_plus_plus_amd.post_training_utils.fine_tune_epoch',
 }
