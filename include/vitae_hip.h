@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define VITAE_ABI_VERSION 50
+#define VITAE_ABI_VERSION 51
 
 /* matrix-core arithmetic of the dense contractions */
 #define VITAE_PREC_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32 (the reference's precision, autocast off at utils/train_one_epoch.py:50) */
@@ -404,7 +404,12 @@ int vitae_noise_gamma(const float* x, const float* noise, float* y, const float*
 
 /* ---- loss chain ----------------------------------------------------------------------------------
  * pred element (b,l,e) lives at pred[b*pred_bstride + l*P + e] (P = p^3*C), so the decoder output
- * with its cls row is read in place (model/vit_autoenc.py:198-201). */
+ * with its cls row is read in place (model/vit_autoenc.py:198-201).
+ * Refusals (ABI 51: the same list for every launcher of this section, returned before anything is enqueued): VITAE_ERR_INVALID_ARG for
+ * a NULL required pointer, B, C, Lz, Hy or Wx <= 0, p <= 0 or an extent that p does not divide (wherever p is an argument),
+ * mask_sum <= 0 or NaN (wherever it is an argument), and B > 65535 where the grid has a workgroup row per batch element
+ * (vitae_recon_loss_*, vitae_unpatchify, vitae_loss_fwd_fused, vitae_loss_bwd_fused, vitae_loss_fwd_bwd, vitae_target_edge;
+ * vitae_sobel_edge_fwd serves any B, vitae_gauss_blur_fwd any BC). */
 int vitae_recon_loss_fwd(const float* pred, long pred_bstride, const float* imgs, const float* mask, double* acc,
                          int B, int C, int Lz, int Hy, int Wx, int p, void* stream);   /* :205-227 */
 int vitae_recon_loss_bwd(const float* pred, long pred_bstride, const float* imgs, const float* mask, const float* hp,
@@ -412,7 +417,9 @@ int vitae_recon_loss_bwd(const float* pred, long pred_bstride, const float* imgs
 int vitae_unpatchify(const float* pred, long pred_bstride, float* vol, int B, int C, int Lz, int Hy, int Wx, int p,
                      void* stream);                                                     /* :115-128 */
 /* separable 3-pass blur == dense k(x)k(x)k conv3d of model/model_utils/gaussian_filter.py:16-26;
- * taps_host is a HOST array (copied into the launch), ntaps odd */
+ * taps_host is a HOST array (copied into the launch), ntaps odd and <= VITAE_MAX_TAPS (else VITAE_ERR_INVALID_ARG).  11 taps and
+ * Wx <= 384 take the LDS-tiled kernels (Wx > 250 asks for more than 64 KB of dynamic LDS: 99,840 bytes at 384); everything else the
+ * one-axis-at-a-time kernel */
 int vitae_gauss_blur_fwd(const float* vol, float* tmp, float* out, const float* taps_host, int ntaps, int BC, int Lz,
                          int Hy, int Wx, void* stream);
 /* edge[B,Lz,Hy,Wx] = sum_c |sobel(vol[:,c])| (model/model_utils/sobel_filter.py:37-45); with edge_ref
@@ -481,7 +488,9 @@ int vitae_bn1d_relu_fwd_split(const float* x, const float* w, const float* b, fl
 int vitae_bn1d_relu_bwd_split(const float* dy, const float* x, const float* y, const float* w, const float* save_mean,
                               const float* save_rstd, float* dx, void* dx_bf16, float* dw_accum, float* db_accum, int R, int D,
                               float* ws, void* stream);
-/* contr = contr_w * (-(mean cos(p1,z2) + mean cos(p2,z1))/2)  (utils/train_one_epoch.py:113-114) */
+/* contr = contr_w * (-(mean cos(p1,z2) + mean cos(p2,z1))/2)  (utils/train_one_epoch.py:113-114); cos(p, z) = <p, z> / (max(|p|, 1e-8)
+ * max(|z|, 1e-8)) (nn.CosineSimilarity).  The backward differentiates exactly that: a row with |p| < 1e-8 gets coef z / (1e-8 max(|z|, 1e-8))
+ * without the - cos p / |p|^2 term (ABI 51; the clamped norm is a constant) */
 int vitae_cosine_loss_fwd(const float* p1, const float* z2, const float* p2, const float* z1, double* acc,
                           const float* hp, float* out1, int R, int D, void* stream);
 int vitae_cosine_loss_bwd(const float* p1, const float* z2, const float* p2, const float* z1, const float* hp,

@@ -565,8 +565,11 @@ __global__ __launch_bounds__(256, 2) void loss_bwd_fused_kernel(const float* __r
     const int x0 = (blockIdx.x % xtiles) * TX, y0 = (blockIdx.x / xtiles) * TY_, z0 = blockIdx.y * TZ, b = blockIdx.z;
     const float ce = 2.f * hp[VITAE_HP_G_EDGE] * inv_count, cr = 2.f * hp[VITAE_HP_G_RECON] * inv_p_masksum;
 
-    // dE at this thread's dG columns (same for every channel); NaN marks "outside the volume"
+    // dE at this thread's dG columns (same for every channel); one bit per column voxel says "inside the volume" (a NaN
+    // in dE is data: a non-finite prediction has to reach dpred, it must not read as "outside")
     float de[NPASS][GZ];
+    unsigned inbits = 0u;
+    static_assert(NPASS * GZ <= 32, "one bit per dG voxel of a thread");
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps) {
         const int col = threadIdx.x + ps * 256;
@@ -576,10 +579,11 @@ __global__ __launch_bounds__(256, 2) void loss_bwd_fused_kernel(const float* __r
 #pragma unroll
         for (int k = 0; k < GZ; ++k) {
             const int gz = z0 - 1 + k;
-            float v = __builtin_nanf("");
+            float v = 0.f;
             if (cin && gz >= 0 && gz < Lz) {
                 const long o = (long)b * V + ((long)gz * Hy + gy) * Wx + gx;
                 v = ce * (Ep[o] - Et[o]);
+                inbits |= 1u << (ps * GZ + k);
             }
             de[ps][k] = v;
         }
@@ -654,7 +658,7 @@ __global__ __launch_bounds__(256, 2) void loss_bwd_fused_kernel(const float* __r
                     sobel_plane(base + vz * VY * VX, VX, A2, B2, C2);
                     const float g0 = A0 + 2.f * A1 + A2, g1 = B0 + 2.f * B1 + B2, g2 = C2 - C0;
                     const float d = de[ps][vz - 2];
-                    const bool in = d == d;
+                    const bool in = (inbits >> (ps * GZ + vz - 2)) & 1u;
                     const float f = d * __builtin_amdgcn_rsqf(g0 * g0 + g1 * g1 + g2 * g2);   // |g| = 0 -> inf -> NaN below
                     const int gi = ((vz - 2) * GY + cy) * GX + cx;
                     sg[0][gi] = in ? f * g0 : 0.f;
@@ -814,7 +818,7 @@ __global__ void cosine_finalize_kernel(const double* __restrict__ acc, const flo
     out[0] = hp[VITAE_HP_CONTR_W] * (float)(-0.5 * acc[VITAE_ACC_COS] * (double)inv_rows);
 }
 
-// dp = g_contr * (-0.5 / R) * ( z/(|p||z|) - cos * p/|p|^2 )
+// dp = g_contr * (-0.5 / R) * ( z/(|p||z|) - cos * p/|p|^2 ), norms clamped at eps; the second term only where |p| >= eps
 __global__ __launch_bounds__(256) void cosine_bwd_kernel(const float* __restrict__ p1, const float* __restrict__ z2,
                                                          const float* __restrict__ p2, const float* __restrict__ z1,
                                                          const float* __restrict__ hp, float* __restrict__ dp1,
@@ -834,9 +838,11 @@ __global__ __launch_bounds__(256) void cosine_bwd_kernel(const float* __restrict
         float dot = 0.f, pp = 0.f, zz = 0.f;
         for (int d = lane; d < D; d += 64) { const float a = p[d], b = z[d]; dot += a * b; pp += a * a; zz += b * b; }
         dot = wave_sum(dot); pp = wave_sum(pp); zz = wave_sum(zz);
-        const float np = fmaxf(sqrtf(pp), eps), nz = fmaxf(sqrtf(zz), eps);
+        const float rp = sqrtf(pp);
+        const float np = fmaxf(rp, eps), nz = fmaxf(sqrtf(zz), eps);
         const float c = dot / (np * nz);
-        const float k1 = coef / (np * nz), k2 = coef * c / (np * np);
+        // below the clamp the norm IS the constant eps: cos = <p, z> / (eps |z|) has no p / |p|^2 term (clamp_min passes no gradient)
+        const float k1 = coef / (np * nz), k2 = rp >= eps ? coef * c / (np * np) : 0.f;
         for (int d = lane; d < D; d += 64) {
             const float v = k1 * z[d] - k2 * p[d];
             if (dp) dp[d] = v;
@@ -853,6 +859,11 @@ inline VolGeom make_geom(int C, int Lz, int Hy, int Wx, int p, long pred_bstride
     return g;
 }
 
+// what every launcher of the chain refuses BEFORE its first launch (make_geom and the kernels divide by p; a grid of (L, B)
+// workgroups holds at most 65535 batch elements)
+inline bool bad_extents(int B, int C, int Lz, int Hy, int Wx) { return B <= 0 || C <= 0 || Lz <= 0 || Hy <= 0 || Wx <= 0; }
+inline bool bad_patches(int Lz, int Hy, int Wx, int p) { return p <= 0 || Lz % p || Hy % p || Wx % p; }
+
 inline int side_blocks() {
     static const int n = getenv("VITAE_SIDE_MAX_BLOCKS") ? atoi(getenv("VITAE_SIDE_MAX_BLOCKS")) : (1 << 30);
     return n < 1 ? 1 : n;
@@ -867,7 +878,7 @@ inline int stream_blocks(long total) {
 
 extern "C" int vitae_recon_loss_fwd(const float* pred, long pred_bstride, const float* imgs, const float* mask,
                                     double* acc, int B, int C, int Lz, int Hy, int Wx, int p, void* stream) {
-    if (!pred || !imgs || !mask || !acc || B <= 0 || p <= 0 || Lz % p || Hy % p || Wx % p) return VITAE_ERR_INVALID_ARG;
+    if (!pred || !imgs || !mask || !acc || bad_extents(B, C, Lz, Hy, Wx) || B > 65535 || bad_patches(Lz, Hy, Wx, p)) return VITAE_ERR_INVALID_ARG;
     VolGeom g = make_geom(C, Lz, Hy, Wx, p, pred_bstride);
     hipLaunchKernelGGL(recon_fwd_kernel, dim3(g.L, B), dim3(256), 0, (hipStream_t)stream, pred, imgs, mask, acc, g);
     return vitae_launch_status();
@@ -876,7 +887,8 @@ extern "C" int vitae_recon_loss_fwd(const float* pred, long pred_bstride, const 
 extern "C" int vitae_recon_loss_bwd(const float* pred, long pred_bstride, const float* imgs, const float* mask,
                                     const float* hp, float* dpred, float mask_sum, int B, int C, int Lz, int Hy,
                                     int Wx, int p, void* stream) {
-    if (!pred || !imgs || !mask || !hp || !dpred || B <= 0 || p <= 0 || mask_sum <= 0.f) return VITAE_ERR_INVALID_ARG;
+    if (!pred || !imgs || !mask || !hp || !dpred || bad_extents(B, C, Lz, Hy, Wx) || B > 65535 || bad_patches(Lz, Hy, Wx, p) || !(mask_sum > 0.f))
+        return VITAE_ERR_INVALID_ARG;
     VolGeom g = make_geom(C, Lz, Hy, Wx, p, pred_bstride);
     const float inv = 1.0f / ((float)g.P * mask_sum);
     hipLaunchKernelGGL(recon_bwd_kernel, dim3(g.L, B), dim3(256), 0, (hipStream_t)stream, pred, imgs, mask, hp, dpred,
@@ -886,7 +898,7 @@ extern "C" int vitae_recon_loss_bwd(const float* pred, long pred_bstride, const 
 
 extern "C" int vitae_unpatchify(const float* pred, long pred_bstride, float* vol, int B, int C, int Lz, int Hy, int Wx,
                                 int p, void* stream) {
-    if (!pred || !vol || B <= 0 || p <= 0 || Lz % p || Hy % p || Wx % p) return VITAE_ERR_INVALID_ARG;
+    if (!pred || !vol || bad_extents(B, C, Lz, Hy, Wx) || B > 65535 || bad_patches(Lz, Hy, Wx, p)) return VITAE_ERR_INVALID_ARG;
     VolGeom g = make_geom(C, Lz, Hy, Wx, p, pred_bstride);
     hipLaunchKernelGGL(unpatchify_kernel, dim3(g.L, B), dim3(256), 0, (hipStream_t)stream, pred, vol, g);
     return vitae_launch_status();
@@ -894,7 +906,8 @@ extern "C" int vitae_unpatchify(const float* pred, long pred_bstride, float* vol
 
 extern "C" int vitae_gauss_blur_fwd(const float* vol, float* tmp, float* out, const float* taps_host, int ntaps,
                                     int BC, int Lz, int Hy, int Wx, void* stream) {
-    if (!vol || !tmp || !out || !taps_host || ntaps <= 0 || ntaps > VITAE_MAX_TAPS || !(ntaps & 1)) return VITAE_ERR_INVALID_ARG;
+    if (!vol || !tmp || !out || !taps_host || ntaps <= 0 || ntaps > VITAE_MAX_TAPS || !(ntaps & 1) || bad_extents(BC, 1, Lz, Hy, Wx))
+        return VITAE_ERR_INVALID_ARG;
     Taps t; t.n = ntaps;
     for (int i = 0; i < ntaps; ++i) t.k[i] = taps_host[i];
     const long total = (long)BC * Lz * Hy * Wx;
@@ -907,6 +920,11 @@ extern "C" int vitae_gauss_blur_fwd(const float* vol, float* tmp, float* out, co
         const int Wp = (Wx + 3) / 4 * 4;
         const size_t lds = (size_t)ROWS * (2 * Wp + 2 * RAD + 2) * sizeof(float);
         const int nbx = cdiv(Hy, TY), tot_xy = nbx * Lz * BC;
+        if (lds > 64 * 1024) {   // Wx > 250 (99,840 bytes at 384): past the default dynamic-LDS limit of a launch
+            static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&blur_xy_kernel<RAD>),
+                                                                hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
+            (void)attr;
+        }
         hipLaunchKernelGGL(blur_xy_kernel<RAD>, dim3(min(tot_xy, side_blocks())), dim3(256), lds, st, vol, tmp, Hy, Wx, TY, t, nbx,
                            tot_xy);
         const long plane = (long)Hy * Wx;
@@ -923,7 +941,7 @@ extern "C" int vitae_gauss_blur_fwd(const float* vol, float* tmp, float* out, co
 
 extern "C" int vitae_sobel_edge_fwd(const float* vol, float* edge, const float* edge_ref, double* acc, int B, int C,
                                     int Lz, int Hy, int Wx, void* stream) {
-    if (!vol || !edge || B <= 0 || C <= 0 || (edge_ref && !acc)) return VITAE_ERR_INVALID_ARG;
+    if (!vol || !edge || bad_extents(B, C, Lz, Hy, Wx) || (edge_ref && !acc)) return VITAE_ERR_INVALID_ARG;
     const int xt = cdiv(Wx, TX), yt = cdiv(Hy, TY_), zt = cdiv(Lz, TZ);
     if (zt <= 65535 && B <= 65535) {
         const int tot = xt * yt * zt * B;
@@ -940,7 +958,8 @@ extern "C" int vitae_sobel_edge_fwd(const float* vol, float* edge, const float* 
 extern "C" int vitae_sobel_edge_bwd(const float* pred_vol, const float* edge_pred, const float* edge_tgt,
                                     const float* hp, float* dG_ws, float* dpred, void* dpred_bf16, long pred_bstride, int B, int C,
                                     int Lz, int Hy, int Wx, int p, void* stream) {
-    if (!pred_vol || !edge_pred || !edge_tgt || !hp || !dG_ws || !dpred || B <= 0) return VITAE_ERR_INVALID_ARG;
+    if (!pred_vol || !edge_pred || !edge_tgt || !hp || !dG_ws || !dpred || bad_extents(B, C, Lz, Hy, Wx) || bad_patches(Lz, Hy, Wx, p))
+        return VITAE_ERR_INVALID_ARG;
     const long total = (long)B * Lz * Hy * Wx;
     VolGeom g = make_geom(C, Lz, Hy, Wx, p, pred_bstride);
     hipStream_t st = (hipStream_t)stream;
@@ -954,7 +973,8 @@ extern "C" int vitae_sobel_edge_bwd(const float* pred_vol, const float* edge_pre
 extern "C" int vitae_loss_fwd_fused(const float* pred, long pred_bstride, const float* imgs, const float* mask,
                                     const float* edge_tgt, float* pred_vol, float* edge_pred, double* acc, int B, int C,
                                     int Lz, int Hy, int Wx, int p, void* stream) {
-    if (!pred || !imgs || !mask || !edge_tgt || !pred_vol || !edge_pred || !acc || B <= 0 || p <= 0 || Lz % p || Hy % p || Wx % p)
+    if (!pred || !imgs || !mask || !edge_tgt || !pred_vol || !edge_pred || !acc || bad_extents(B, C, Lz, Hy, Wx) || B > 65535 ||
+        bad_patches(Lz, Hy, Wx, p))
         return VITAE_ERR_INVALID_ARG;
     VolGeom g = make_geom(C, Lz, Hy, Wx, p, pred_bstride);
     hipStream_t st = (hipStream_t)stream;
@@ -973,8 +993,8 @@ extern "C" int vitae_loss_bwd_fused(const float* pred, const float* pred_vol, co
                                     const float* edge_tgt, const float* hp, float* dG_ws, float* dpred, void* dpred_bf16,
                                     float* nonfinite_flag, long pred_bstride, float mask_sum, int B, int C, int Lz, int Hy,
                                     int Wx, int p, void* stream) {
-    if (!pred || !pred_vol || !imgs || !mask || !edge_pred || !edge_tgt || !hp || !dpred || B <= 0 || p <= 0 || mask_sum <= 0.f ||
-        Lz % p || Hy % p || Wx % p)
+    if (!pred || !pred_vol || !imgs || !mask || !edge_pred || !edge_tgt || !hp || !dpred || bad_extents(B, C, Lz, Hy, Wx) || B > 65535 ||
+        bad_patches(Lz, Hy, Wx, p) || !(mask_sum > 0.f))
         return VITAE_ERR_INVALID_ARG;
     VolGeom g = make_geom(C, Lz, Hy, Wx, p, pred_bstride);
     const long total = (long)B * Lz * Hy * Wx;
@@ -1005,7 +1025,7 @@ extern "C" int vitae_loss_bwd_fused(const float* pred, const float* pred_vol, co
 
 extern "C" int vitae_loss_finalize(const double* acc, const float* hp, float* out4, float mask_sum, long edge_count,
                                    void* stream) {
-    if (!acc || !hp || !out4 || mask_sum <= 0.f || edge_count <= 0) return VITAE_ERR_INVALID_ARG;
+    if (!acc || !hp || !out4 || !(mask_sum > 0.f) || edge_count <= 0) return VITAE_ERR_INVALID_ARG;
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, hp, out4, 1.0f / mask_sum,
                        1.0f / (float)edge_count);
     return vitae_launch_status();

@@ -504,8 +504,8 @@ extern "C" int vitae_loss_fwd_bwd_supported(int C, int Lz, int Hy, int Wx, int p
 extern "C" int vitae_loss_fwd_bwd(const float* pred, long pred_bstride, const float* imgs, const float* mask, const float* edge_tgt,
                                   const float* hp, float* dpred, void* dpred_bf16, float* nonfinite_flag, double* acc,
                                   float mask_sum, int B, int C, int Lz, int Hy, int Wx, int p, void* stream) {
-    if (!pred || !imgs || !mask || !edge_tgt || !hp || (!dpred && !dpred_bf16) || !acc || B <= 0 || B > 65535 || p <= 0 || mask_sum <= 0.f ||
-        Lz % p || Hy % p || Wx % p)
+    if (!pred || !imgs || !mask || !edge_tgt || !hp || (!dpred && !dpred_bf16) || !acc || B <= 0 || B > 65535 || C <= 0 || Lz <= 0 || Hy <= 0 ||
+        Wx <= 0 || p <= 0 || !(mask_sum > 0.f) || Lz % p || Hy % p || Wx % p)
         return VITAE_ERR_INVALID_ARG;
     if (!vitae_loss_fwd_bwd_supported(C, Lz, Hy, Wx, p) || pred_bstride >= (1L << 31) || (pred_bstride & 3) ||
         ((uintptr_t)pred & 15) || ((uintptr_t)dpred & 15) || ((uintptr_t)dpred_bf16 & 7))
