@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define VITAE_ABI_VERSION 51
+#define VITAE_ABI_VERSION 52
 
 /* matrix-core arithmetic of the dense contractions */
 #define VITAE_PREC_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32 (the reference's precision, autocast off at utils/train_one_epoch.py:50) */
@@ -401,6 +401,27 @@ int vitae_affine_resample(const float* x, float* y, const float* mats, const dou
                           int Lz, int Hy, int Wx, void* stream);
 int vitae_noise_gamma(const float* x, const float* noise, float* y, const float* stds, const float* gammas, int B, long n,
                       void* stream);
+/* ---- the fourth augmentation of the fine-tuning scripts (post_training_utils/fine_tune_epoch.py:248-255: tio.RandomAffine(),
+ * tio.RandomBlur(), tio.RandomNoise(std=0.1), tio.RandomGamma(log_gamma=(-0.3, 0.3))) (ABI 52; csrc/blur.hip).  torchio blurs every
+ * channel of an item with scipy.ndimage.gaussian_filter(channel, std_b): restated, parity unpinned as for the three above.
+ * vitae_random_blur: y[b,c] = the separable blur of x[b,c] with item b's own taps, axis 0 (Lz) first, then 1 (Hy), then 2 (Wx):
+ *   out[i] = sum_{k=0..2r} w[k] in[reflect(i + k - r)],  r = radii[b*3 + axis],  w = taps[(b*3 + axis)*VITAE_BLUR_MAX_TAPS + k],
+ *   reflect = scipy's 'reflect' border (d c b a | a b c d | d c b a; periodic, so any extent >= 1 serves any radius).  The first
+ *   product starts the sum and the others are added in index order, so a radius-0 axis with w[0] = 1 is an exact copy and two calls
+ *   with one table give the same bits.  taps and radii are DEVICE arrays; radii_host is the HOST copy of radii the call is judged
+ *   and sized from (device memory is not read to validate; the kernels clamp what they read to the host's maxima).  tmp holds the
+ *   intermediate [B,C,Lz,Hy,Wx] and may be NULL when no item blurs along Lz or none along Hy / Wx; when every radius is 0 the
+ *   call is one device-to-device copy.  Not in place.  Refusals, before anything is enqueued: VITAE_ERR_INVALID_ARG for a NULL
+ *   required pointer, x == y, tmp == x or y, an extent or B or C <= 0, a negative radius; VITAE_ERR_UNSUPPORTED_SHAPE for B or C
+ *   > 65535, an extent > 2^30 and for a radius above VITAE_BLUR_MAX_RADIUS (sigma <= 4.09; the default range (0, 2) draws at most 8).
+ *   The tile constants say where the kernels' seams fall (tests/test_random_blur.py builds a shape from them). */
+#define VITAE_BLUR_MAX_RADIUS 16
+#define VITAE_BLUR_MAX_TAPS 33
+#define VITAE_BLUR_TILE_Z 128 /* output planes a workgroup of the Lz pass */
+#define VITAE_BLUR_TILE_Y 32  /* output rows ... */
+#define VITAE_BLUR_TILE_X 128 /* ... and columns a workgroup of the Hy / Wx pass */
+int vitae_random_blur(const float* x, float* tmp, float* y, const float* taps, const int* radii, const int* radii_host, int B, int C,
+                      int Lz, int Hy, int Wx, void* stream);
 
 /* ---- loss chain ----------------------------------------------------------------------------------
  * pred element (b,l,e) lives at pred[b*pred_bstride + l*P + e] (P = p^3*C), so the decoder output

@@ -1,4 +1,4 @@
-"""The augmentations of the pre-training scripts as batch operations on volumes already in HBM.
+"""The augmentations of the pre-training and fine-tuning scripts as batch operations on volumes already in HBM.
 
 The reference augments one item at a time in DataLoader workers with torchio
 (k_fold_training_scripts/k_fold_cross_valid_combined_brats.py:93-97: ``tio.RandomAffine()``, ``tio.RandomNoise(std=0.1)``,
@@ -6,10 +6,12 @@ The reference augments one item at a time in DataLoader workers with torchio
 of fp32 per volume and view over PCIe afterwards.  Here the raw batch is uploaded once and both views are produced on
 the GPU: the classes below keep torchio's names, constructor arguments and parameter distributions, draw the random
 parameters on the host (one set per item, ``torch`` CPU generator) and launch deterministic HIP kernels
-(``csrc/input.hip``) for the whole batch.
+(``csrc/input.hip``) for the whole batch.  The fine-tuning script composes a fourth transform between the affine and the noise
+(post_training_utils/fine_tune_epoch.py:248-255: ``tio.RandomBlur()``): ``RandomBlur`` below, ``csrc/blur.hip``.
 
 torchio / SimpleITK are third-party code that is absent here: the conventions restated (and what is and is not pinned)
-are listed in ``oracle/augment_ref.py``.
+are listed in ``oracle/augment_ref.py``; RandomBlur's are in its docstring and in ``tests/test_random_blur.py``, which holds them
+against scipy (the library torchio's blur calls).
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from .._abi import VitaeError, lib
+from .._abi import VitaeError, const, lib
 from .input_pipeline import normalize_data
 
 
@@ -112,6 +114,85 @@ class RandomAffine(_Random):
         s, d, t = self.get_params(x.shape[0])
         self.last_params = {'scales': s, 'degrees': d, 'translation': t}
         return self.apply(x, self.matrices(s, d, t, x.shape[2:]))
+
+
+class RandomBlur(_Random):
+    """``tio.RandomBlur``: per item three standard deviations, one per axis, each ~ U(its range), in voxels (a bare tensor has
+    spacing 1); every channel of the item is blurred with ``scipy.ndimage.gaussian_filter(channel, std)``: one axis after the
+    other, radius int(4 sigma + 0.5), weights normalised in float64, border mode 'reflect'.  ``std``: a scalar d means (0, d), a
+    pair that range on all three axes, six values (a0, b0, a1, b1, a2, b2)."""
+
+    MAX_RADIUS = const('VITAE_BLUR_MAX_RADIUS')
+    MAX_TAPS = const('VITAE_BLUR_MAX_TAPS')
+
+    def __init__(self, std=(0, 2), generator: Optional[torch.Generator] = None):
+        super().__init__(generator)
+        if isinstance(std, (int, float)):
+            v = (0.0, float(std)) * 3
+        else:
+            v = tuple(float(t) for t in std)
+            if len(v) == 2:
+                v = v * 3
+            if len(v) != 6:
+                raise ValueError(f'std: a number, a pair or six values, not {len(v)}')
+        self.std = tuple((v[2 * d], v[2 * d + 1]) for d in range(3))
+        for a, b in self.std:
+            if a < 0 or b < 0:
+                raise ValueError(f'std: negative bound in ({a}, {b})')
+            if a > b:
+                raise ValueError(f'std: lower bound {a} above upper bound {b}')
+
+    def get_params(self, B: int) -> torch.Tensor:
+        """[B, 3]: three draws per item, item after item, each mapped into its axis's range"""
+        u = torch.empty(B, 3, dtype=torch.float32).uniform_(0, 1, generator=self.generator)
+        lo = torch.tensor([a for a, _ in self.std], dtype=torch.float32)
+        hi = torch.tensor([b for _, b in self.std], dtype=torch.float32)
+        return torch.minimum(lo + (hi - lo) * u, hi)
+
+    @staticmethod
+    def tap_table(stds) -> Tuple[torch.Tensor, torch.Tensor]:
+        """stds [B, 3] -> (taps [B, 3, MAX_TAPS] fp32: the 2 r + 1 weights of each axis, computed and normalised in float64 and
+        rounded once, zeros behind them; radii [B, 3] int32).  sigma <= 1e-15 is scipy's skipped axis: radius 0, weight 1."""
+        stds = torch.as_tensor(stds, dtype=torch.float64).reshape(-1, 3)
+        B = stds.shape[0]
+        taps = torch.zeros(B, 3, RandomBlur.MAX_TAPS, dtype=torch.float32)
+        radii = torch.zeros(B, 3, dtype=torch.int32)
+        for b in range(B):
+            for d in range(3):
+                s = float(stds[b, d])
+                if not s >= 0:
+                    raise ValueError(f'RandomBlur: standard deviation {s}')
+                r = int(4.0 * s + 0.5) if s > 1e-15 else 0
+                if r > RandomBlur.MAX_RADIUS:
+                    raise VitaeError(f'RandomBlur: standard deviation {s:g} needs a radius of {r} voxels; the kernels serve radii '
+                                     f'up to {RandomBlur.MAX_RADIUS} (VITAE_BLUR_MAX_RADIUS)')
+                if r > 0:
+                    k = torch.arange(-r, r + 1, dtype=torch.float64)
+                    w = torch.exp(-0.5 * k * k / (s * s))
+                    taps[b, d, :2 * r + 1] = (w / w.sum()).float()
+                else:
+                    taps[b, d, 0] = 1.0
+                radii[b, d] = r
+        return taps, radii
+
+    def apply(self, x: torch.Tensor, stds: torch.Tensor) -> torch.Tensor:
+        taps, radii = self.tap_table(stds)            # a radius above the cap raises here, before anything is launched
+        x = _check(x)
+        B, C, Lz, Hy, Wx = x.shape
+        if radii.shape[0] != B:
+            raise VitaeError(f'RandomBlur: {radii.shape[0]} sets of standard deviations for a batch of {B}')
+        y = torch.empty_like(x)
+        rmax = radii.max(dim=0).values
+        tmp = torch.empty_like(x) if int(rmax[0]) > 0 and int(rmax[1:].max()) > 0 else None   # only a z AND a y / x pass need it
+        taps_d, radii_d = taps.to(x.device), radii.to(x.device)
+        lib.vitae_random_blur(x.data_ptr(), None if tmp is None else tmp.data_ptr(), y.data_ptr(), taps_d.data_ptr(),
+                              radii_d.data_ptr(), radii.data_ptr(), B, C, Lz, Hy, Wx, _stream(x))
+        return y
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        stds = self.get_params(x.shape[0])
+        self.last_params = {'std': stds}
+        return self.apply(x, stds)
 
 
 def _noise_gamma(x, noise, stds, gammas):
