@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define VITAE_ABI_VERSION 52
+#define VITAE_ABI_VERSION 53
 
 /* matrix-core arithmetic of the dense contractions */
 #define VITAE_PREC_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32 (the reference's precision, autocast off at utils/train_one_epoch.py:50) */
@@ -306,6 +306,16 @@ int vitae_vit_assemble_bwd(const float* dx, float* dtok, void* dtok_bf16, float*
  * written: mode 1 (global pool, x[:, 1:].mean(1)): rows 1..N-1 = dsel[b] / (N - 1), row 0 = 0; mode 0 (cls row, x[:, 0]):
  * row 0 = dsel[b], the others 0.  D % 4 == 0, 16-byte aligned arrays. */
 int vitae_token_select_bwd(const float* dsel, float* dx, int B, int N, int D, int mode, void* stream);
+/* The hand-over from the head into the bf16-activation backward chain (ABI 53), one launch: dx [B*N, D] exactly as
+ * vitae_token_select_bwd writes it, dx_bf16 [Mpad, D] = its round-to-nearest-even copy with rows B*N .. Mpad-1 written as ZERO
+ * (the dy operand of vitae_linear_bwd_pair_glds, which reduces dW over Mpad rows), and colsum[D] (optional) OVERWRITTEN with the
+ * column sums of dx: the fc2 bias gradient of the top block.  Every token row of a sample holds one value, so a sample's share of
+ * a column sum is (N - 1) dsel[b] / (N - 1) rounded once (mode 1) or dsel[b] (mode 0); the samples are added in order b = 0, 1, ..
+ * inside one thread: no atomics, bitwise reproducible.  16-byte accesses: D % 8 == 0 (else VITAE_ERR_UNSUPPORTED_SHAPE), 16-byte
+ * aligned arrays.  VITAE_ERR_INVALID_ARG, before anything is enqueued, for a NULL dsel / dx / dx_bf16, a non-positive extent,
+ * Mpad < B*N, Mpad % 64 != 0, a mode other than 0 / 1, or mode 1 with N < 2. */
+int vitae_token_select_bwd16(const float* dsel, float* dx, void* dx_bf16, float* colsum, int B, int N, int Mpad, int D, int mode,
+                             void* stream);
 /* xd[B,L+1,Dd]: mask-token fill + unshuffle + decoder_pos_embed (model/vit_autoenc.py:184-190) */
 int vitae_decoder_assemble_fwd(const float* e, const float* mask_token, const float* dpos, const int* ids_restore,
                                float* xd, int B, int L, int keep, int Dd, void* stream);

@@ -9,7 +9,13 @@ Mixup of a batch (vitae_mixup_pairs against the torch three-op formulation x.fli
 criteria (HipCrossEntropyLoss / HipSoftCrossEntropyWithWeightsLoss against torch's, forward + backward on [16, 2] logits) and
 evaluate() in volumes/s (batch 16, 4 batches, bf16 and fp32).
 
-    python tools/finetune_bench.py [step] [mixup] [criterion] [evaluate]      (no argument: every row)"""
+    python tools/finetune_bench.py [step] [mixup] [criterion] [evaluate]      (no argument: every row)
+
+``--activations bf16`` (with ``step``): the bf16-activation training route (``VisionTransformer3D(precision='bf16',
+activations='bf16')``) against the default bf16 route, timed alternating A / B on two models in this process, with the inference
+forward of the same model beside them; ``--batch B`` picks one batch size (default 4 and 16).
+
+    python tools/finetune_bench.py step --activations bf16 [--batch 4]"""
 import os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -17,7 +23,35 @@ from vit_ae_plus_plus_amd.model.vit import VisionTransformer3D
 from vit_ae_plus_plus_amd.utils.lr_decay import param_groups_lrd
 
 WARMUP, ITERS = 5, 50
-ROWS = sys.argv[1:] or ['step', 'mixup', 'criterion', 'evaluate']
+ARGV = sys.argv[1:]
+
+
+def _option(name):
+    """Value of ``name VALUE`` on the command line (removed from ARGV), or None."""
+    if name not in ARGV:
+        return None
+    i = ARGV.index(name)
+    if i + 1 >= len(ARGV):
+        sys.exit(f'finetune_bench.py: {name} needs a value')
+    value = ARGV[i + 1]
+    del ARGV[i:i + 2]
+    return value
+
+
+def _usage(msg):
+    sys.exit(f'finetune_bench.py: {msg}\nusage: finetune_bench.py [step] [mixup] [criterion] [evaluate] | step --activations bf16 [--batch B]')
+
+
+ACTIVATIONS, BATCH = _option('--activations'), _option('--batch')
+ROWS = ARGV or ['step', 'mixup', 'criterion', 'evaluate']
+if [r for r in ROWS if r not in ('step', 'mixup', 'criterion', 'evaluate')]:
+    _usage(f'unknown argument(s) {[r for r in ROWS if r not in ("step", "mixup", "criterion", "evaluate")]}')
+if ACTIVATIONS is not None and ACTIVATIONS != 'bf16':
+    _usage(f"--activations takes 'bf16' (got {ACTIVATIONS!r})")
+if (ACTIVATIONS or BATCH) and ROWS != ['step']:
+    _usage('--activations / --batch go with the step row alone: finetune_bench.py step --activations bf16 [--batch B]')
+if BATCH is not None and (not ACTIVATIONS or not BATCH.isdigit() or int(BATCH) < 1):
+    _usage('--batch takes a positive integer and goes with --activations')
 
 
 def timed(fn):
@@ -121,7 +155,49 @@ def evaluate_rows():
               f'{B * n_batches / t[0] * 1e3:.0f} volumes/s', flush=True)
 
 
-if 'step' in ROWS:
+def act16_rows():
+    """The two bf16 training routes in turns: forward + backward, the step with AdamW, kept MiB; and the inference forward."""
+    for B in ([int(BATCH)] if BATCH else [4, 16]):
+        x = torch.randn(B, 4, 96, 96, 96, device='cuda')
+        y = torch.randint(0, 2, (B,), device='cuda')
+        crit = torch.nn.CrossEntropyLoss()
+        fns, models = {}, {}
+        for act in (None, ACTIVATIONS):
+            m = VisionTransformer3D(volume_size=96, patch_size=16, in_chans=4, num_classes=2, global_pool=True, precision='bf16',
+                                    activations=act, drop_path_rate=0.1).cuda().train()
+            torch.nn.init.normal_(m.head.weight, std=0.02)        # a zero head gives zero encoder gradients
+            opt = torch.optim.AdamW(param_groups_lrd(m, 0.05, m.no_weight_decay(), 0.75), lr=1e-3)
+
+            def fwd_bwd(m=m, opt=opt):
+                opt.zero_grad(set_to_none=True)
+                crit(m(x), y).backward()
+
+            def step(m=m, opt=opt, fwd_bwd=fwd_bwd):
+                fwd_bwd()
+                opt.step()
+
+            fns[act], models[act] = (fwd_bwd, step), m
+
+        def infer(m=models[ACTIVATIONS]):
+            with torch.no_grad():
+                m(x)
+
+        fb = timed_ab(fns[None][0], fns[ACTIVATIONS][0])
+        st = timed_ab(fns[None][1], fns[ACTIVATIONS][1])
+        inf = timed(infer)
+        for (name, act), a, b in zip((('default', None), (ACTIVATIONS, ACTIVATIONS)), fb, st):
+            print(f'bf16 B={B} activations={name!s:8s}: forward+backward {a[0]:.2f} ms ({a[1]:.2f} .. {a[2]:.2f}), step with AdamW {b[0]:.2f} ms '
+                  f'({b[1]:.2f} .. {b[2]:.2f}), {B / b[0] * 1e3:.0f} volumes/s, kept {models[act]._trainer.stats["kept_bytes"] / 2 ** 20:.0f} MiB',
+                  flush=True)
+        print(f'bf16 B={B} inference forward {inf[0]:.2f} ms ({inf[1]:.2f} .. {inf[2]:.2f}); forward+backward / forward: default '
+              f'{fb[0][0] / inf[0]:.1f}x, {ACTIVATIONS} {fb[1][0] / inf[0]:.1f}x; new / default {fb[1][0] / fb[0][0]:.3f} (forward+backward), '
+              f'{st[1][0] / st[0][0]:.3f} (step)', flush=True)
+        del fns, models, x
+
+
+if 'step' in ROWS and ACTIVATIONS:
+    act16_rows()
+elif 'step' in ROWS:
     for precision in ('fp32', 'bf16'):
         for B in (4, 16):
             for fix_backbone in (False, True):

@@ -236,6 +236,9 @@ def _init_vit_weights(module: nn.Module, name: str = '', head_bias: float = 0.):
         nn.init.ones_(module.weight)
 
 
+_KEEP = object()       # set_precision: 'leave the activations route as it is'
+
+
 class VisionTransformer3D(nn.Module):
     """Encoder-only 3-D ViT that consumes the pre-trained weights (reference model/vit.py:147-298): same constructor,
     state-dict keys and ``forward_features`` / ``forward`` results; the arithmetic runs on the HIP kernels.
@@ -256,12 +259,14 @@ class VisionTransformer3D(nn.Module):
     ``precision``: 'fp32' (exact-fp32 MFMA, matches the CPU reference to ~1e-6), 'fp32x3' (fp32 operands split into bf16 hi + lo
     inside the GEMMs: the same results to a few 1e-6) or 'bf16' (bf16 MFMA operands with
     fp32 accumulation — the counterpart of the ``torch.cuda.amp.autocast()`` the reference wraps around
-    forward_features, utils/feature_extraction.py:35-36, and around the fine-tune forward, fine_tune_epoch.py:61)."""
+    forward_features, utils/feature_extraction.py:35-36, and around the fine-tune forward, fine_tune_epoch.py:61).
+    ``activations``: None (default) or 'bf16' — with ``precision='bf16'``, train on bf16 activations and the LDS-DMA GEMM family
+    (``HipEncoderTrainer16``: 40 instead of 64 bytes kept per token row, block and embedding column); see ``set_precision``."""
 
     def __init__(self, volume_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, representation_size=None, distilled=False,
                  drop_rate=0., attn_drop_rate=0., drop_path_rate=0., embed_layer=PatchEmbed3D, norm_layer=None,
-                 act_layer=None, weight_init='', global_pool=False, precision=None):
+                 act_layer=None, weight_init='', global_pool=False, precision=None, activations=None):
         super().__init__()
         if distilled or representation_size:
             raise NotImplementedError('distilled / representation_size variants are not built for MI355X')
@@ -295,9 +300,12 @@ class VisionTransformer3D(nn.Module):
             self.fc_norm = norm_layer(embed_dim)
             del self.norm  # as the reference: fc_norm replaces norm (model/vit.py:218-221)
         self._precision = precision or 'fp32'
+        self._activations = None
         self._encoder = None
         self._trainer = None
         self.init_weights(weight_init)
+        if activations is not None:
+            self.set_precision(self._precision, activations=activations)
 
     def init_weights(self, mode=''):
         head_bias = -math.log(self.num_classes) if 'nlhb' in mode else 0.
@@ -320,8 +328,25 @@ class VisionTransformer3D(nn.Module):
         self.num_classes = num_classes
         self.head = nn.Linear(self.embed_dim, num_classes) if num_classes > 0 else nn.Identity()
 
-    def set_precision(self, precision: str):
+    def set_precision(self, precision: str, activations=_KEEP):
+        """``activations``: None — training keeps fp32 activations and runs the generic Linear launchers (the constructor's default);
+        'bf16' — training runs on producer-written bf16 GEMM operands and the LDS-DMA GEMM family (``HipEncoderTrainer16``).  Left out,
+        the current choice stays: ``set_precision('bf16')`` in a k-fold loop does not drop the route, and ``set_precision('fp32')`` on a
+        model that trains on bf16 activations raises instead of changing the route silently (pass ``activations=None`` with it).
+        'bf16' is accepted only for a model that route serves (precision 'bf16'; embed_dim, MLP hidden size and in_chans * patch_size^3
+        multiples of 64; head size 32 or 64): anything else raises here and changes nothing.  Inference is not affected (it takes the
+        bf16-operand forward by itself)."""
+        if activations is _KEEP:
+            activations = self._activations
+        if activations is not None:
+            if activations != 'bf16':
+                raise VitaeError(f"unknown activations {activations!r} (None or 'bf16')")
+            from ..encoder import act16_refusal_for
+            why = act16_refusal_for(self, precision)
+            if why:
+                raise VitaeError(why)
         self._precision = precision
+        self._activations = activations
         self._encoder = None
         self._trainer = None
 
@@ -336,8 +361,8 @@ class VisionTransformer3D(nn.Module):
             enc = self._encoder_params()
             if any(p.requires_grad for _, p in enc):
                 if self._trainer is None:
-                    from ..encoder import HipEncoderTrainer
-                    self._trainer = HipEncoderTrainer(self, self._precision)
+                    from ..encoder import HipEncoderTrainer, HipEncoderTrainer16
+                    self._trainer = (HipEncoderTrainer16 if self._activations == 'bf16' else HipEncoderTrainer)(self, self._precision)
                 return _EncoderFunction.apply(self._trainer, tuple(n for n, _ in enc), x, *(p for _, p in enc))
         if self._encoder is None:
             from ..encoder import HipEncoder
