@@ -1,15 +1,20 @@
-"""Encoder-only inference on MI355X: the kernel sequence behind ``VisionTransformer3D.forward_features``
-(reference model/vit.py:265-284, driven by utils/feature_extraction.py:9-45 after pre-training).
+"""The all-token encoder of ``VisionTransformer3D`` on MI355X (reference model/vit.py:265-284): feature extraction (driven by
+utils/feature_extraction.py:9-45 after pre-training) and fine-tuning (post_training_utils/fine_tune_epoch.py:34-100).
 
 Same kernels as the training engine's encoder, unmasked (every patch is kept, N = L + 1 tokens):
 patch gather -> patch-embedding GEMM -> cls/pos assembly -> depth x [LN, qkv, attention, proj(+res), LN,
-fc1+GELU, fc2(+res)] -> global-pool mean + fc_norm, or norm of the cls rows.  Nothing is kept for a
-backward pass, so two activation buffers ping-pong through the blocks.
+fc1+GELU, fc2(+res)] -> global-pool mean + fc_norm, or norm of the cls rows.
 
-bf16 mode (the counterpart of the reference's ``torch.cuda.amp.autocast()`` around forward_features)
-keeps GEMM operands in bf16 written by their producers and runs every Linear on the LDS-DMA GEMM when
-all contraction lengths are multiples of 64; otherwise, and in fp32 mode, the generic Linear launcher
-(exact-fp32 MFMA or bf16 MFMA with fp32 activations) is used.
+Two activation routes, each with ONE block forward (``HipEncoder._block32`` / ``_block16``) over a dictionary of buffers:
+  fp32 activations  every Linear on the generic launcher (exact-fp32 MFMA, split bf16 hi + lo, or bf16 MFMA on fp32 activations);
+  bf16 activations  GEMM operands in bf16 written by their producers, every Linear on the LDS-DMA GEMM.  ``act16_refusal`` is the
+                    rule: bf16 precision (the counterpart of the reference's ``torch.cuda.amp.autocast()``), all contraction lengths
+                    multiples of 64, an MFMA head size.
+
+``HipEncoder`` is inference: it takes the bf16 route whenever the rule allows, keeps nothing for a backward and runs every block on
+one cached set of buffers, two activation buffers ping-ponging.  ``HipEncoderTrainer`` (fp32 route) and ``HipEncoderTrainer16`` (bf16
+route) share the frame ``_Trainer``: the same embedding, block forward and pooling on per-call buffers that the caller keeps, and a
+``backward`` each, which is the place to read a route's launch order.
 """
 from __future__ import annotations
 
@@ -20,16 +25,46 @@ import torch
 from ._abi import CONSTS as _C, VitaeError, lib
 
 PREC = {'fp32': _C['VITAE_PREC_F32'], 'bf16': _C['VITAE_PREC_BF16'], 'fp32x3': _C['VITAE_PREC_BF16X3']}
-EPI_NONE, EPI_GELU = _C['VITAE_EPI_NONE'], _C['VITAE_EPI_GELU']
+EPI_NONE, EPI_GELU, EPI_DGELU = _C['VITAE_EPI_NONE'], _C['VITAE_EPI_GELU'], _C['VITAE_EPI_DGELU']
+EPI_AUX_BF16, EPI_AUX_DERIV = _C['VITAE_EPI_AUX_BF16'], _C['VITAE_EPI_AUX_DERIV']     # flags, OR-ed into an epilogue above bit 3
+_EMBED = ('cls_token', 'pos_embed', 'patch_embed.proj.weight', 'patch_embed.proj.bias')
 
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _pad64(M):
+    return (M + 63) // 64 * 64
+
+
+def act16_refusal(precision, embed_dim, hidden, patch_dim, head_dim):
+    """Why the bf16-activation route does not serve this model (None: it does): bf16 arithmetic, every contraction length a multiple
+    of the LDS-DMA GEMM's 64-wide k-tile, an MFMA head size."""
+    if precision != 'bf16':
+        return f"activations='bf16' needs precision='bf16' (got {precision!r})"
+    bad = {k: v for k, v in (('embed_dim', embed_dim), ('MLP hidden size', hidden), ('in_chans * patch_size^3', patch_dim)) if v % 64}
+    if bad:
+        return f"activations='bf16' needs multiples of 64, got {bad}"
+    if head_dim not in (32, 64):
+        return f"activations='bf16' needs a head size of 32 or 64 (got {head_dim})"
+    return None
+
+
+def act16_refusal_for(module, precision, in_chans=None):
+    """``act16_refusal`` for a ``VisionTransformer3D`` (``in_chans``: of the input at hand; default: of the patch embedding)."""
+    pe = module.patch_embed
+    hidden = module.blocks[0].mlp.fc1.out_features if len(module.blocks) else module.embed_dim
+    c = pe.proj.in_channels if in_chans is None else in_chans
+    return act16_refusal(precision, module.embed_dim, hidden, c * pe.patch_size[0] * pe.patch_size[1] * pe.patch_size[2],
+                         module.embed_dim // module.num_heads)
+
+
 class HipEncoder:
-    """Sequences the encoder kernels for one ``VisionTransformer3D`` instance (weights are read from the
-    module's parameters at call time; bf16 copies are cached per parameter version)."""
+    """Sequences the encoder kernels for one ``VisionTransformer3D`` instance (weights are read from the module's parameters at call
+    time; bf16 copies are cached per parameter version) and runs them for inference.  The launch helpers of both routes live here;
+    ``self.buf`` holds the split-K scratch of the route in use (``'ws'``: generic launchers, ``'ws16'``: LDS-DMA family, whose ticket
+    words start as zero and are left zero by every launch) and, for inference, the cached activation buffers."""
 
     def __init__(self, module, precision: str = 'fp32'):
         if precision not in PREC:
@@ -38,7 +73,7 @@ class HipEncoder:
         self.m = module
         self.precision, self.prec = precision, PREC[precision]
         self._w16: Dict[str, Tuple[int, torch.Tensor]] = {}
-        self._B = None
+        self._B = None          # (batch size, device) the inference buffers were made for
         self.buf: Dict[str, torch.Tensor] = {}
         self._split: Dict[Tuple, int] = {}
 
@@ -63,10 +98,11 @@ class HipEncoder:
 
     # ------------------------------------------------------------------ workspace
     def _alloc(self, B: int):
+        """The buffers of an inference forward at batch size B, cached until B or the device changes.  One set serves every block,
+        so the two LayerNorms of a block share their output and statistics (``y1`` is ``y2``, ``mean1`` is ``mean2``)."""
         m = self.m
         L, D, H, P = m.patch_embed.num_patches, m.embed_dim, self.hidden, self.P
-        N = L + 1
-        M = B * N
+        M = B * (L + 1)
         if self._B == (B, self.device):
             return
         self._B = (B, self.device)
@@ -76,55 +112,52 @@ class HipEncoder:
         b['ids'] = torch.arange(L, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
         b['tok'] = f(B * L, D)
         b['xa'], b['xb'], b['xmid'] = f(M, D), f(M, D), f(M, D)
-        b['qkv'], b['o'], b['lse'] = f(M, 3 * D), f(M, D), f(B * m.num_heads * N)
-        b['mean'], b['rstd'] = f(max(M, B)), f(max(M, B))
+        b['qkv'], b['o'], b['lse'] = f(M, 3 * D), f(M, D), f(B * m.num_heads * (L + 1))
+        b['mean1'], b['rstd1'] = f(M), f(M)
         b['hpre'] = f(M, H)
         b['pool'], b['feat'] = f(B, D), f(B, D)
         if self.act16:
             z16 = lambda *s: torch.zeros(*s, dtype=torch.bfloat16, device=dev)
             b['patches_16'] = z16(B * L, P)
-            b['y_16'], b['o_16'], b['act_16'] = z16(M, D), z16(M, D), z16(M, H)
+            b['y1_16'], b['o_16'], b['act_16'] = z16(M, D), z16(M, D), z16(M, H)
+            b['y2_16'] = b['y1_16']
             b['ws16'] = torch.zeros(1 << 22, dtype=torch.float32, device=dev)
         else:
-            b['patches'], b['y'], b['act'] = f(B * L, P), f(M, D), f(M, H)
+            b['patches'], b['y1'], b['act'] = f(B * L, P), f(M, D), f(M, H)
+            b['y2'] = b['y1']
             b['ws'] = f(1 << 22)
+        b['mean2'], b['rstd2'] = b['mean1'], b['rstd1']
 
     # ------------------------------------------------------------------ launch helpers
+    def _fit_split(self, key, pick, need, capacity):
+        """The split-K of one GEMM shape, cached under ``key``: what the planner ``pick()`` proposes, shrunk until the ``need(s)``
+        floats of scratch it takes fit into ``capacity``.  Call sites look into ``_split`` first, so this runs once per shape."""
+        s = pick()
+        while s > 1 and need(s) > capacity:
+            s -= 1
+        self._split[key] = s
+        return s
+
     def _g16(self, x16, wname, bname, M, N, K, y=None, y16=None, epi=EPI_NONE, aux=None, res=None):
-        key = ('g', M, N, K, epi)
-        s = self._split.get(key)
-        if s is None:
-            s = 1 if (epi & 15) == EPI_GELU else lib.vitae_gemm_glds_pick_split_k(M, N, K)     # (flags are OR-ed in above bit 3)
-            while s > 1 and lib.vitae_gemm_glds_ws_floats(M, N, s) > self.buf['ws16'].numel():
-                s -= 1
-            self._split[key] = s
+        """y / y16 [M, N] = epi(x16 W16^T + b) (+ res) on the LDS-DMA GEMM; a GELU epilogue cannot be split."""
+        ws, key = self.buf['ws16'], ('g', M, N, K, epi)
+        s = self._split.get(key) or self._fit_split(
+            key, lambda: 1 if (epi & 15) == EPI_GELU else lib.vitae_gemm_glds_pick_split_k(M, N, K),
+            lambda s: lib.vitae_gemm_glds_ws_floats(M, N, s), ws.numel())
         lib.vitae_gemm_glds(1, 1, _ptr(x16), K, self._bf16(wname), K, _ptr(y), N, _ptr(y16), N, M, N, K,
-                            _ptr(self._param(bname)), _ptr(res), N, epi, _ptr(aux), N, 0, s, self.buf['ws16'].data_ptr(), None,
-                            self.stream)
+                            _ptr(self._param(bname)), _ptr(res), N, epi, _ptr(aux), N, 0, s, ws.data_ptr(), None, self.stream)
 
     def _lin(self, x, wname, bname, y, M, N, K, epi=EPI_NONE, aux=None, res=None):
-        key = ('l', M, N, K, epi)
-        s = self._split.get(key)
-        if s is None:
-            s = 1 if epi != EPI_NONE else lib.vitae_gemm_pick_split_k(M, N, K)
-            while s > 1 and s * M * N > self.buf['ws'].numel():
-                s -= 1
-            self._split[key] = s
+        """y [M, N] = epi(x W^T + b) (+ res) on the generic launcher; any epilogue forces one split."""
+        ws, key = self.buf['ws'], ('l', M, N, K, epi)
+        s = self._split.get(key) or self._fit_split(
+            key, lambda: 1 if epi != EPI_NONE else lib.vitae_gemm_pick_split_k(M, N, K), lambda s: s * M * N, ws.numel())
         lib.vitae_linear_fwd(self.prec, _ptr(x), _ptr(self._param(wname)), _ptr(self._param(bname)), _ptr(y), M, N, K, epi,
-                             _ptr(aux), _ptr(res), s, self.buf['ws'].data_ptr(), self.stream)
+                             _ptr(aux), _ptr(res), s, ws.data_ptr(), self.stream)
 
-    def _ln(self, x, pre, y, y16, M, D):
-        b = self.buf
+    def _ln(self, x, pre, y, y16, mean, rstd, M, D):
         lib.vitae_layernorm_fwd(_ptr(x), _ptr(self._param(pre + 'weight')), _ptr(self._param(pre + 'bias')), _ptr(y), _ptr(y16),
-                                _ptr(b['mean']), _ptr(b['rstd']), M, D, self.eps, self.stream)
-
-    def _sdpa(self, B, N):
-        b, m = self.buf, self.m
-        if self.prec == PREC['bf16'] and self.hd in (32, 64):
-            lib.vitae_sdpa_mfma_fwd(_ptr(b['qkv']), _ptr(b['o']), _ptr(b['o_16']) if self.act16 else None, _ptr(b['lse']), B, N,
-                                    m.num_heads, self.hd, self.stream)
-        else:
-            lib.vitae_sdpa_fwd(_ptr(b['qkv']), _ptr(b['o']), _ptr(b['lse']), B, N, m.num_heads, self.hd, self.stream)
+                                _ptr(mean), _ptr(rstd), M, D, self.eps, self.stream)
 
     # ------------------------------------------------------------------ forward
     def _begin(self, x: torch.Tensor):
@@ -148,83 +181,105 @@ class HipEncoder:
         self.eps = m.ln_eps
         return B, C, Lz, Hy, Wx, ps
 
+    def _embed(self, xc, vol, ids, patches, patches16, tok, x0):
+        """Volume ``xc`` of geometry ``vol`` (what ``_begin`` returned) -> token rows ``x0`` [B (L + 1), D].  The patch operand is
+        ``patches`` (fp32, generic launcher) or ``patches16`` (bf16, LDS-DMA GEMM); the other one is None."""
+        B, L, D = vol[0], self.m.patch_embed.num_patches, self.m.embed_dim
+        lib.vitae_gather_patches(_ptr(xc), _ptr(ids), _ptr(patches), _ptr(patches16), *vol, L, self.stream)
+        if patches16 is not None:
+            self._g16(patches16, 'patch_embed.proj.weight', 'patch_embed.proj.bias', B * L, D, self.P, y=tok)
+        else:
+            self._lin(patches, 'patch_embed.proj.weight', 'patch_embed.proj.bias', tok, B * L, D, self.P)
+        lib.vitae_encoder_assemble_fwd(_ptr(tok), _ptr(self._param('cls_token')), _ptr(self._param('pos_embed')), _ptr(ids),
+                                       _ptr(x0), B, L, L, D, self.stream)
+
+    def _block32(self, q, k, x_in, x_out, aux_epi, B, N, D, H):
+        """Block ``q`` on fp32 activations: x_in -> x_out through the buffers ``k``.  ``aux_epi``: what fc1 leaves in ``hpre`` beside
+        its GELU (nothing more: the pre-activation; ``EPI_AUX_DERIV``: GELU' of it, what a backward multiplies by)."""
+        M, heads = B * N, self.m.num_heads
+        self._ln(x_in, q + 'norm1.', k['y1'], None, k['mean1'], k['rstd1'], M, D)
+        self._lin(k['y1'], q + 'attn.qkv.weight', q + 'attn.qkv.bias', k['qkv'], M, 3 * D, D)
+        if self.prec == PREC['bf16'] and self.hd in (32, 64):
+            lib.vitae_sdpa_mfma_fwd(_ptr(k['qkv']), _ptr(k['o']), None, _ptr(k['lse']), B, N, heads, self.hd, self.stream)
+        else:
+            lib.vitae_sdpa_fwd(_ptr(k['qkv']), _ptr(k['o']), _ptr(k['lse']), B, N, heads, self.hd, self.stream)
+        self._lin(k['o'], q + 'attn.proj.weight', q + 'attn.proj.bias', k['xmid'], M, D, D, res=x_in)
+        self._ln(k['xmid'], q + 'norm2.', k['y2'], None, k['mean2'], k['rstd2'], M, D)
+        self._lin(k['y2'], q + 'mlp.fc1.weight', q + 'mlp.fc1.bias', k['act'], M, H, D, epi=EPI_GELU | aux_epi, aux=k['hpre'])
+        self._lin(k['act'], q + 'mlp.fc2.weight', q + 'mlp.fc2.bias', x_out, M, D, H, res=k['xmid'])
+
+    def _block16(self, q, k, x_in, x_out, qkv16, aux_epi, aux_key, B, N, D, H):
+        """Block ``q`` on bf16 activations: x_in -> x_out through the buffers ``k``.  ``qkv16``: q | k | v are kept in bf16
+        (``qkv_16``) and the attention reads them there; otherwise it reads the fp32 ``qkv``.  fc1 leaves in ``k[aux_key]`` what
+        ``aux_epi`` says beside its GELU (nothing more: the fp32 pre-activation; ``EPI_AUX_BF16 | EPI_AUX_DERIV``: bf16 GELU' of it,
+        what the fc2 input-gradient epilogue multiplies by)."""
+        M, heads = B * N, self.m.num_heads
+        self._ln(x_in, q + 'norm1.', None, k['y1_16'], k['mean1'], k['rstd1'], M, D)
+        if qkv16:
+            self._g16(k['y1_16'], q + 'attn.qkv.weight', q + 'attn.qkv.bias', M, 3 * D, D, y16=k['qkv_16'])
+            lib.vitae_sdpa_mfma_fwd_bf16in(_ptr(k['qkv_16']), _ptr(k['o']), _ptr(k['o_16']), _ptr(k['lse']), B, N, heads, self.hd,
+                                           self.stream)
+        else:
+            self._g16(k['y1_16'], q + 'attn.qkv.weight', q + 'attn.qkv.bias', M, 3 * D, D, y=k['qkv'])
+            lib.vitae_sdpa_mfma_fwd(_ptr(k['qkv']), _ptr(k['o']), _ptr(k['o_16']), _ptr(k['lse']), B, N, heads, self.hd, self.stream)
+        self._g16(k['o_16'], q + 'attn.proj.weight', q + 'attn.proj.bias', M, D, D, y=k['xmid'], res=x_in)
+        self._ln(k['xmid'], q + 'norm2.', None, k['y2_16'], k['mean2'], k['rstd2'], M, D)
+        self._g16(k['y2_16'], q + 'mlp.fc1.weight', q + 'mlp.fc1.bias', M, H, D, y16=k['act_16'], epi=EPI_GELU | aux_epi, aux=k[aux_key])
+        self._g16(k['act_16'], q + 'mlp.fc2.weight', q + 'mlp.fc2.bias', M, D, H, y=x_out, res=k['xmid'])
+
+    def _pool_norm(self, x, pool, feat, mean, rstd, B, N, D):
+        """Token rows x -> features [B, D]; the final norm's statistics go to ``mean`` / ``rstd``."""
+        if self.m.global_pool:
+            lib.vitae_mean_pool_tokens(_ptr(x), _ptr(pool), B, N, D, 1, self.stream)
+            self._ln(pool, 'fc_norm.', feat, None, mean, rstd, B, D)
+        else:
+            # LayerNorm is row-wise: normalising only the cls rows equals norm(x)[:, 0] (model/vit.py:281-282)
+            pool.copy_(x.view(B, N, D)[:, 0])
+            self._ln(pool, 'norm.', feat, None, mean, rstd, B, D)
+
     @torch.no_grad()
     def forward_features(self, x: torch.Tensor) -> torch.Tensor:
         m = self.m
-        B, C, Lz, Hy, Wx, ps = self._begin(x)
-        L, D = m.patch_embed.num_patches, m.embed_dim
-        N, M = L + 1, B * (L + 1)
-        H, P = self.hidden, self.P
-        self.act16 = (self.prec == PREC['bf16'] and all(v % 64 == 0 for v in (D, H, P)) and self.hd in (32, 64))
+        vol = self._begin(x)
+        B, N, D, H = vol[0], m.patch_embed.num_patches + 1, m.embed_dim, self.hidden
+        self.act16 = act16_refusal(self.precision, D, H, self.P, self.hd) is None
         self._alloc(B)
-        b, st = self.buf, self.stream
-        xc = x.contiguous().float()
-        a16 = self.act16
-        lib.vitae_gather_patches(_ptr(xc), _ptr(b['ids']), None if a16 else _ptr(b['patches']), _ptr(b['patches_16']) if a16 else None,
-                                 B, C, Lz, Hy, Wx, ps, L, st)
-        if a16:
-            self._g16(b['patches_16'], 'patch_embed.proj.weight', 'patch_embed.proj.bias', B * L, D, P, y=b['tok'])
-        else:
-            self._lin(b['patches'], 'patch_embed.proj.weight', 'patch_embed.proj.bias', b['tok'], B * L, D, P)
-        lib.vitae_encoder_assemble_fwd(_ptr(b['tok']), _ptr(self._param('cls_token')), _ptr(self._param('pos_embed')),
-                                       _ptr(b['ids']), _ptr(b['xa']), B, L, L, D, st)
+        b = self.buf
+        self._embed(x.contiguous().float(), vol, b['ids'], b.get('patches'), b.get('patches_16'), b['tok'], b['xa'])
         cur, nxt = b['xa'], b['xb']
         for i in range(len(m.blocks)):
-            q = f'blocks.{i}.'
-            if a16:
-                self._ln(cur, q + 'norm1.', None, b['y_16'], M, D)
-                self._g16(b['y_16'], q + 'attn.qkv.weight', q + 'attn.qkv.bias', M, 3 * D, D, y=b['qkv'])
-                self._sdpa(B, N)
-                self._g16(b['o_16'], q + 'attn.proj.weight', q + 'attn.proj.bias', M, D, D, y=b['xmid'], res=cur)
-                self._ln(b['xmid'], q + 'norm2.', None, b['y_16'], M, D)
-                self._g16(b['y_16'], q + 'mlp.fc1.weight', q + 'mlp.fc1.bias', M, H, D, y16=b['act_16'], epi=EPI_GELU, aux=b['hpre'])
-                self._g16(b['act_16'], q + 'mlp.fc2.weight', q + 'mlp.fc2.bias', M, D, H, y=nxt, res=b['xmid'])
+            if self.act16:
+                self._block16(f'blocks.{i}.', b, cur, nxt, False, EPI_NONE, 'hpre', B, N, D, H)
             else:
-                self._ln(cur, q + 'norm1.', b['y'], None, M, D)
-                self._lin(b['y'], q + 'attn.qkv.weight', q + 'attn.qkv.bias', b['qkv'], M, 3 * D, D)
-                self._sdpa(B, N)
-                self._lin(b['o'], q + 'attn.proj.weight', q + 'attn.proj.bias', b['xmid'], M, D, D, res=cur)
-                self._ln(b['xmid'], q + 'norm2.', b['y'], None, M, D)
-                self._lin(b['y'], q + 'mlp.fc1.weight', q + 'mlp.fc1.bias', b['act'], M, H, D, epi=EPI_GELU, aux=b['hpre'])
-                self._lin(b['act'], q + 'mlp.fc2.weight', q + 'mlp.fc2.bias', nxt, M, D, H, res=b['xmid'])
+                self._block32(f'blocks.{i}.', b, cur, nxt, EPI_NONE, B, N, D, H)
             cur, nxt = nxt, cur
-        if m.global_pool:
-            lib.vitae_mean_pool_tokens(_ptr(cur), _ptr(b['pool']), B, N, D, 1, st)
-            self._ln(b['pool'], 'fc_norm.', b['feat'], None, B, D)
-        else:
-            # LayerNorm is row-wise: normalising only the cls rows equals norm(x)[:, 0] (model/vit.py:281-282)
-            b['pool'].copy_(cur.view(B, N, D)[:, 0])
-            self._ln(b['pool'], 'norm.', b['feat'], None, B, D)
+        self._pool_norm(cur, b['pool'], b['feat'], b['mean1'], b['rstd1'], B, N, D)
         return b['feat'].clone()
 
 
-EPI_DGELU, EPI_AUX_DERIV = _C['VITAE_EPI_DGELU'], _C['VITAE_EPI_AUX_DERIV']
-_EMBED = ('cls_token', 'pos_embed', 'patch_embed.proj.weight', 'patch_embed.proj.bias')
+class _Trainer(HipEncoder):
+    """What the two fine-tuning routes share.  ``forward_keep`` runs the inference launch sequence on buffers allocated per call and
+    returns, beside the features, what ``backward`` reads: the caller owns it (and hangs it on the autograd context), so any number of
+    forwards may precede a backward.  Only split-K scratch and the patch index table live on the trainer.  Gradients are produced for
+    the parameters named in ``needs`` only: a frozen Linear has no weight-gradient launch, and blocks below the lowest trainable
+    parameter are neither kept (they run on one shared set of buffers) nor walked.  ``backward`` is the route's own, after
+    ``_backward_head``.  ``stats`` counts the calls and the bytes the last forward kept (tests and tools/finetune_bench.py read it).
 
-
-class HipEncoderTrainer(HipEncoder):
-    """Training counterpart of ``HipEncoder`` (fine-tuning, reference post_training_utils/fine_tune_epoch.py:34-100):
-    ``forward_keep`` runs the same launch sequence on the generic Linear launchers and keeps, per block, what the backward
-    reads; ``backward`` walks the blocks from the top in the launch order of ``HipMAEEngine._block_bwd`` — eager launches
-    on the current stream, no side streams, no graph capture.
-
-    The kept activations are allocated per call and returned to the caller (who hangs them on the autograd context), so any
-    number of forwards may precede a backward.  Only split-K scratch and the patch index table live on the trainer.
-    Gradients are produced for the parameters named in ``needs`` only: a frozen Linear has no weight-gradient launch, and
-    blocks below the lowest trainable parameter are neither kept nor walked.  ``stats`` counts the calls and the bytes the
-    last forward kept (tests read it; nothing else does)."""
+    A route supplies ``ROUTE``, ``act16``, ``SCRATCH`` / ``SCRATCH_ZEROED`` (its split-K scratch in ``buf`` and whether that starts as
+    zero), ``_refusal``, ``_patch_operand``, ``_block_bufs``, ``_block`` and ``backward``; the bf16 route also ``_zero_pads``."""
 
     WS_FLOATS = 1 << 24        # split-K scratch, 64 MiB (as the training engine's)
 
-    def __init__(self, module, precision: str = 'fp32'):
+    def __init__(self, module, precision):
         super().__init__(module, precision)
-        self.act16 = False     # fp32 activations on the generic launchers; HipEncoderTrainer16 is the bf16-activation route
-        self.stats = {'forwards': 0, 'backwards': 0, 'kept_bytes': 0, 'route': 'fp32-activations'}
+        self.stats = {'forwards': 0, 'backwards': 0, 'kept_bytes': 0, 'route': self.ROUTE}
 
     def _workspace(self, B: int, L: int):
-        if self._B != self.device:          # scratch does not depend on the batch: forwards of different sizes may interleave
-            self._B = self.device
-            self.buf = {'ws': torch.empty(self.WS_FLOATS, dtype=torch.float32, device=self.device)}
+        """Scratch (it does not depend on the batch: forwards of different sizes may interleave) -> the patch index table of batch B."""
+        ws = self.buf.get(self.SCRATCH)
+        if ws is None or ws.device != self.device:
+            make = torch.zeros if self.SCRATCH_ZEROED else torch.empty
+            self.buf = {self.SCRATCH: make(self.WS_FLOATS, dtype=torch.float32, device=self.device)}
         if ('ids', B) not in self.buf:
             self.buf['ids', B] = torch.arange(L, dtype=torch.int32, device=self.device).repeat(B, 1).contiguous()
         return self.buf['ids', B]
@@ -247,77 +302,118 @@ class HipEncoderTrainer(HipEncoder):
                 lo = min(lo, int(n.split('.')[1]))
         return False, lo
 
-    # ------------------------------------------------------------------ forward
-    def _ln_keep(self, x, pre, y, mean, rstd, M, D):
-        lib.vitae_layernorm_fwd(_ptr(x), _ptr(self._param(pre + 'weight')), _ptr(self._param(pre + 'bias')), _ptr(y), None,
-                                _ptr(mean), _ptr(rstd), M, D, self.eps, self.stream)
-
-    def _block_keep(self, q, x_in, B, N, D, H):
-        f, M, heads = self._f, B * N, self.m.num_heads
-        k = {'x_in': x_in, 'mean1': f(M), 'rstd1': f(M), 'y1': f(M, D), 'qkv': f(M, 3 * D), 'o': f(M, D), 'lse': f(B * heads * N),
-             'xmid': f(M, D), 'mean2': f(M), 'rstd2': f(M), 'y2': f(M, D), 'hpre': f(M, H), 'act': f(M, H)}
-        x_out = f(M, D)
-        self._ln_keep(x_in, q + 'norm1.', k['y1'], k['mean1'], k['rstd1'], M, D)
-        self._lin(k['y1'], q + 'attn.qkv.weight', q + 'attn.qkv.bias', k['qkv'], M, 3 * D, D)
-        if self.prec == PREC['bf16'] and self.hd in (32, 64):
-            lib.vitae_sdpa_mfma_fwd(_ptr(k['qkv']), _ptr(k['o']), None, _ptr(k['lse']), B, N, heads, self.hd, self.stream)
-        else:
-            lib.vitae_sdpa_fwd(_ptr(k['qkv']), _ptr(k['o']), _ptr(k['lse']), B, N, heads, self.hd, self.stream)
-        self._lin(k['o'], q + 'attn.proj.weight', q + 'attn.proj.bias', k['xmid'], M, D, D, res=x_in)
-        self._ln_keep(k['xmid'], q + 'norm2.', k['y2'], k['mean2'], k['rstd2'], M, D)
-        # aux <- GELU'(pre-activation): what the backward multiplies by (as the training engine keeps it)
-        self._lin(k['y2'], q + 'mlp.fc1.weight', q + 'mlp.fc1.bias', k['act'], M, H, D, epi=EPI_GELU | EPI_AUX_DERIV, aux=k['hpre'])
-        self._lin(k['act'], q + 'mlp.fc2.weight', q + 'mlp.fc2.bias', x_out, M, D, H, res=k['xmid'])
-        return k, x_out
-
     def forward_keep(self, x: torch.Tensor, needs: Dict[str, bool]):
         """-> (features [B, D], kept): ``kept`` is what ``backward`` needs, owned by the caller."""
         m = self.m
-        B, C, Lz, Hy, Wx, ps = self._begin(x)
+        vol = self._begin(x)
+        B, C = vol[0], vol[1]
         L, D, H, P = m.patch_embed.num_patches, m.embed_dim, self.hidden, self.P
         N, M, depth = L + 1, B * (L + 1), len(m.blocks)
-        if D % 4:
-            raise VitaeError('embed_dim must be a multiple of 4')
+        why = self._refusal(C)
+        if why:         # (the input's channel count is only known here)
+            raise VitaeError(why)
         ids = self._workspace(B, L)
-        f, st = self._f, self.stream
+        f = self._f
         embed, lo = self.lowest_trainable(needs, depth)
         xc = x.detach().contiguous().float()
-        patches, tok, cur = f(B * L, P), f(B * L, D), f(M, D)
-        lib.vitae_gather_patches(_ptr(xc), _ptr(ids), _ptr(patches), None, B, C, Lz, Hy, Wx, ps, L, st)
-        self._lin(patches, 'patch_embed.proj.weight', 'patch_embed.proj.bias', tok, B * L, D, P)
-        lib.vitae_encoder_assemble_fwd(_ptr(tok), _ptr(self._param('cls_token')), _ptr(self._param('pos_embed')), _ptr(ids),
-                                       _ptr(cur), B, L, L, D, st)
-        blocks = {}
+        patches, patches16 = self._patch_operand(B * L, P)
+        tok, cur = f(B * L, D), f(M, D)
+        # the blocks the backward will walk keep their own buffers, the ones below share one set
+        blocks, shared = {}, None
+        if self.act16:          # every Mpad-row operand of the call before its first launch, for one zeroing of all pad rows
+            blocks = {i: self._block_bufs(B, N, D, H) for i in range(min(lo, depth), depth)}
+            shared = self._block_bufs(B, N, D, H) if min(lo, depth) > 0 else None
+            self._zero_pads()
+        self._embed(xc, vol, ids, patches, patches16, tok, cur)
         for i in range(depth):
-            kb, cur = self._block_keep(f'blocks.{i}.', cur, B, N, D, H)
-            if i >= lo:
-                blocks[i] = kb
+            x_in, cur = cur, f(M, D)
+            k = blocks.get(i) if i >= lo else shared
+            if k is None:       # fp32 route: allocated block by block, while the GPU runs the launches already issued
+                k = self._block_bufs(B, N, D, H)
+                if i >= lo:
+                    blocks[i] = k
+                else:
+                    shared = k
+            k['x_in'] = x_in
+            self._block(f'blocks.{i}.', k, x_in, cur, B, N, D, H)
         pool, feat, mean, rstd = f(B, D), f(B, D), f(B), f(B)
-        if m.global_pool:
-            lib.vitae_mean_pool_tokens(_ptr(cur), _ptr(pool), B, N, D, 1, st)
-            self._ln_keep(pool, 'fc_norm.', feat, mean, rstd, B, D)
-        else:
-            pool.copy_(cur.view(B, N, D)[:, 0])
-            self._ln_keep(pool, 'norm.', feat, mean, rstd, B, D)
+        self._pool_norm(cur, pool, feat, mean, rstd, B, N, D)
         kept = {'geom': (B, L, D, H, P), 'needs': dict(needs), 'params': self.sd, 'embed': embed, 'lo': lo, 'blocks': blocks,
                 'versions': {n: p._version for n, p in self.sd.items() if not n.startswith('head.')},
-                'patches': patches if needs.get('patch_embed.proj.weight') else None, 'pool': pool, 'mean': mean, 'rstd': rstd}
+                'patches': (patches if patches16 is None else patches16) if needs.get('patch_embed.proj.weight') else None,
+                'pool': pool, 'mean': mean, 'rstd': rstd}
         self.stats['forwards'] += 1
-        self.stats['kept_bytes'] = 4 * (sum(t.numel() for kb in blocks.values() for t in kb.values())
-                                        + sum(t.numel() for t in (kept['patches'], pool, mean, rstd) if t is not None))
+        self.stats['kept_bytes'] = (sum(t.numel() * t.element_size() for kb in blocks.values() for t in kb.values())
+                                    + sum(t.numel() * t.element_size() for t in (kept['patches'], pool, mean, rstd) if t is not None))
         return feat, kept
+
+    def _ln_bwd(self, grads, needs, dy, x, pre, mean, rstd, dx, M, D, dx_accumulate, dx16=None, dx_colsum=None):
+        """LayerNorm backward: dx (+)= ..., optionally its bf16 copy ``dx16`` and its column sums added to ``dx_colsum``."""
+        dw, db = self._z(D), self._z(D)             # the launcher adds its column partials
+        lib.vitae_layernorm_bwd(_ptr(dy), _ptr(x), _ptr(self._param(pre + 'weight')), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dw),
+                                _ptr(db), _ptr(dx16), _ptr(dx_colsum), M, D, dx_accumulate, self.stream)
+        if needs.get(pre + 'weight'):
+            grads[pre + 'weight'] = dw
+        if needs.get(pre + 'bias'):
+            grads[pre + 'bias'] = db
+
+    def _backward_head(self, kept, dfeat: torch.Tensor):
+        """How every ``backward`` begins: geometry of the call, the stale-parameter check, the final norm's backward.
+        -> (grads so far, dpool [B, D]; None when no block and no embedding parameter is trainable: the backward is complete)."""
+        B, L, D, H, P = kept['geom']
+        self.device = dfeat.device
+        self.stream = torch.cuda.current_stream(dfeat.device).cuda_stream
+        self.sd = kept['params']
+        stale = [n for n, v in kept['versions'].items() if self.sd[n]._version != v]
+        # the backward reads the weights (and their bf16 copies, keyed by version) again: they must be the ones the forward used (as
+        # autograd checks for its own ops)
+        if stale:
+            raise VitaeError(f'parameters were modified in place between forward and backward: {stale[:3]} ...')
+        self._workspace(B, L)
+        grads: Dict[str, torch.Tensor] = {}
+        dfeat = dfeat.contiguous().float()
+        dpool = self._f(B, D)
+        self._ln_bwd(grads, kept['needs'], dfeat, kept['pool'], 'fc_norm.' if self.m.global_pool else 'norm.', kept['mean'],
+                     kept['rstd'], dpool, B, D, 0)
+        self.stats['backwards'] += 1
+        if not kept['embed'] and kept['lo'] >= len(self.m.blocks):
+            return grads, None
+        return grads, dpool
+
+
+class HipEncoderTrainer(_Trainer):
+    """Fine-tuning on fp32 activations and the generic Linear launchers (any precision): ``backward`` walks the blocks from the top
+    in the launch order of ``HipMAEEngine._block_bwd`` — separate input-gradient, weight-gradient and column-sum launches, eager on
+    the current stream, no side streams, no graph capture.  ``HipEncoderTrainer16`` is the bf16-activation route."""
+
+    ROUTE, SCRATCH, SCRATCH_ZEROED = 'fp32-activations', 'ws', False
+    act16 = False
+
+    def __init__(self, module, precision: str = 'fp32'):
+        super().__init__(module, precision)
+
+    def _refusal(self, in_chans):
+        return 'embed_dim must be a multiple of 4' if self.m.embed_dim % 4 else None
+
+    def _patch_operand(self, T, P):
+        return self._f(T, P), None
+
+    def _block_bufs(self, B, N, D, H):
+        """What one block keeps, except its input."""
+        f, M = self._f, B * N
+        return {'mean1': f(M), 'rstd1': f(M), 'y1': f(M, D), 'qkv': f(M, 3 * D), 'o': f(M, D), 'lse': f(B * self.m.num_heads * N),
+                'xmid': f(M, D), 'mean2': f(M), 'rstd2': f(M), 'y2': f(M, D), 'hpre': f(M, H), 'act': f(M, H)}
+
+    def _block(self, q, k, x_in, x_out, B, N, D, H):
+        self._block32(q, k, x_in, x_out, EPI_AUX_DERIV, B, N, D, H)
 
     # ------------------------------------------------------------------ backward
     def _split_bwd(self, M, N, K):
         """Split of the reduction (length K) of a backward GEMM with an [M, N] result, fitted to the scratch buffer."""
         key = ('b', M, N, K)
-        s = self._split.get(key)
-        if s is None:
-            s = (lib.vitae_gemm_bf16x3_pick_split_k if self.prec == PREC['fp32x3'] else lib.vitae_gemm_pick_split_k)(M, N, K)
-            while s > 1 and s * M * N > self.buf['ws'].numel():
-                s -= 1
-            self._split[key] = s
-        return s
+        return self._split.get(key) or self._fit_split(
+            key, lambda: (lib.vitae_gemm_bf16x3_pick_split_k if self.prec == PREC['fp32x3'] else lib.vitae_gemm_pick_split_k)(M, N, K),
+            lambda s: s * M * N, self.buf['ws'].numel())
 
     def _lin_bwd(self, grads, needs, dy, wname, bname, x, dx, M, N, K, epi=EPI_NONE, aux=None):
         """Backward of y = x W^T + b given dy [M, N]: dW = dy^T x and db = colsum(dy) for trainable parameters only,
@@ -334,37 +430,16 @@ class HipEncoderTrainer(HipEncoder):
             lib.vitae_linear_bwd_input(self.prec, _ptr(dy), _ptr(self._param(wname)), _ptr(dx), M, N, K, epi, _ptr(aux), 0,
                                        self._split_bwd(M, K, N), ws, self.stream)
 
-    def _ln_bwd(self, grads, needs, dy, x, pre, mean, rstd, dx, M, D, dx_accumulate):
-        dw, db = self._z(D), self._z(D)             # the launcher adds its column partials
-        lib.vitae_layernorm_bwd(_ptr(dy), _ptr(x), _ptr(self._param(pre + 'weight')), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dw),
-                                _ptr(db), None, None, M, D, dx_accumulate, self.stream)
-        if needs.get(pre + 'weight'):
-            grads[pre + 'weight'] = dw
-        if needs.get(pre + 'bias'):
-            grads[pre + 'bias'] = db
-
     def backward(self, kept, dfeat: torch.Tensor) -> Dict[str, torch.Tensor]:
         """d loss / d features [B, D] -> {parameter name: gradient} for the trainable parameters of the encoder."""
+        grads, dpool = self._backward_head(kept, dfeat)
+        if dpool is None:
+            return grads
         m = self.m
         B, L, D, H, P = kept['geom']
         N, M, depth, heads = L + 1, B * (L + 1), len(m.blocks), m.num_heads
-        self.device = dfeat.device
-        self.stream = torch.cuda.current_stream(dfeat.device).cuda_stream
-        self.sd = kept['params']
-        stale = [n for n, v in kept['versions'].items() if self.sd[n]._version != v]
-        if stale:       # the backward reads the weights again: they must be the ones the forward used (as autograd checks for its own ops)
-            raise VitaeError(f'parameters were modified in place between forward and backward: {stale[:3]} ...')
-        self._workspace(B, L)
         needs, f, st = kept['needs'], self._f, self.stream
-        grads: Dict[str, torch.Tensor] = {}
-        dfeat = dfeat.contiguous().float()
-        dpool = f(B, D)
-        self._ln_bwd(grads, needs, dfeat, kept['pool'], 'fc_norm.' if m.global_pool else 'norm.', kept['mean'], kept['rstd'],
-                     dpool, B, D, 0)
-        self.stats['backwards'] += 1
         embed, lo = kept['embed'], kept['lo']
-        if not embed and lo >= depth:
-            return grads
         dx = f(M, D)
         lib.vitae_token_select_bwd(_ptr(dpool), _ptr(dx), B, N, D, 1 if m.global_pool else 0, st)
         dh, dy, do, dqkv, delta = f(M, H), f(M, D), f(M, D), f(M, 3 * D), f(B * heads * N)
@@ -396,37 +471,12 @@ class HipEncoderTrainer(HipEncoder):
         return {n: g for n, g in grads.items() if g is not None}
 
 
-EPI_AUX_BF16 = _C['VITAE_EPI_AUX_BF16']
-
-
-def act16_refusal(precision, embed_dim, hidden, patch_dim, head_dim):
-    """Why the bf16-activation route does not serve this model (None: it does) — the rule ``HipEncoder.forward_features`` applies
-    to ``act16``: bf16 arithmetic, every contraction length a multiple of the LDS-DMA GEMM's 64-wide k-tile, an MFMA head size."""
-    if precision != 'bf16':
-        return f"activations='bf16' needs precision='bf16' (got {precision!r})"
-    bad = {k: v for k, v in (('embed_dim', embed_dim), ('MLP hidden size', hidden), ('in_chans * patch_size^3', patch_dim)) if v % 64}
-    if bad:
-        return f"activations='bf16' needs multiples of 64, got {bad}"
-    if head_dim not in (32, 64):
-        return f"activations='bf16' needs a head size of 32 or 64 (got {head_dim})"
-    return None
-
-
-def act16_refusal_for(module, precision, in_chans=None):
-    """``act16_refusal`` for a ``VisionTransformer3D`` (``in_chans``: of the input at hand; default: of the patch embedding)."""
-    pe = module.patch_embed
-    hidden = module.blocks[0].mlp.fc1.out_features if len(module.blocks) else module.embed_dim
-    c = pe.proj.in_channels if in_chans is None else in_chans
-    return act16_refusal(precision, module.embed_dim, hidden, c * pe.patch_size[0] * pe.patch_size[1] * pe.patch_size[2],
-                         module.embed_dim // module.num_heads)
-
-
-class HipEncoderTrainer16(HipEncoderTrainer):
-    """The bf16-activation training route (``VisionTransformer3D(precision='bf16', activations='bf16')``): the contracts of
-    ``HipEncoderTrainer``, the kernels of the MAE engine's ``_block_fwd16`` / ``_block_bwd16`` (non-grouped form).  Every Linear runs
-    on the LDS-DMA GEMM with bf16 operands written by their producers — LayerNorm's bf16 output, the qkv GEMM's bf16 q | k | v, the
-    attention's ``o_16``, fc1's bf16 GELU and bf16 GELU' — and its backward is one paired launch (input gradient + weight gradient)
-    whose dy operand the previous launch wrote in bf16.  Bias gradients ride on those launches (``dy_colsum`` / ``dx_colsum``).
+class HipEncoderTrainer16(_Trainer):
+    """Fine-tuning on bf16 activations (``VisionTransformer3D(precision='bf16', activations='bf16')``): the kernels of the MAE engine's
+    ``_block_fwd16`` / ``_block_bwd16`` (non-grouped form).  Every Linear runs on the LDS-DMA GEMM with bf16 operands written by their
+    producers — LayerNorm's bf16 output, the qkv GEMM's bf16 q | k | v, the attention's ``o_16``, fc1's bf16 GELU and bf16 GELU' — and
+    its backward is one paired launch (input gradient + weight gradient) whose dy operand the previous launch wrote in bf16.  Bias
+    gradients ride on those launches (``dy_colsum`` / ``dx_colsum``).
 
     Kept per token row and block: x_in and xmid in fp32 (LayerNorm backward), o in fp32 (attention backward) and, in bf16, y1, q | k | v,
     o, y2, GELU' and the activation: 40 D bytes against 64 D, plus the row statistics.
@@ -438,31 +488,27 @@ class HipEncoderTrainer16(HipEncoderTrainer):
     launch computes the input gradient alone; its bias gradient then comes from a launch that does not depend on the weight
     gradient (fc1: the column sums of fc2's input-gradient epilogue; qkv: the attention backward's)."""
 
+    ROUTE, SCRATCH, SCRATCH_ZEROED = 'bf16-activations', 'ws16', True
+    act16 = True
+
     def __init__(self, module, precision: str = 'bf16'):
         super().__init__(module, precision)
-        why = act16_refusal_for(module, precision)
+        why = self._refusal(None)
         if why:
             raise VitaeError(why)
-        self.act16 = True
-        self.stats['route'] = 'bf16-activations'
         self._pads = []
 
-    def _workspace(self, B: int, L: int):
-        if self._B != self.device:
-            self._B = self.device
-            # split-K scratch of the LDS-DMA family: its ticket words start as zero and every launch leaves them zero (HipEncoder._alloc)
-            self.buf = {'ws16': torch.zeros(self.WS_FLOATS, dtype=torch.float32, device=self.device)}
-        if ('ids', B) not in self.buf:
-            self.buf['ids', B] = torch.arange(L, dtype=torch.int32, device=self.device).repeat(B, 1).contiguous()
-        return self.buf['ids', B]
+    def _refusal(self, in_chans):
+        return act16_refusal_for(self.m, self.precision, in_chans)
 
     def _e16(self, *shape):
         return torch.empty(*shape, dtype=torch.bfloat16, device=self.device)
 
-    def _z16(self, M, Mpad, W):
-        """A bf16 GEMM operand of M rows in a buffer of Mpad: the producers write rows < M only; the pad rows wait for ``_zero_pads``."""
-        t = self._e16(Mpad, W)
-        if Mpad > M:
+    def _z16(self, M, W):
+        """A bf16 GEMM operand of M rows in a buffer of M rounded up to 64: the producers write rows < M only; the pad rows wait for
+        ``_zero_pads``."""
+        t = self._e16(_pad64(M), W)
+        if t.shape[0] > M:
             self._pads.append(t[M:])
         return t
 
@@ -473,88 +519,28 @@ class HipEncoderTrainer16(HipEncoderTrainer):
             torch._foreach_zero_(self._pads)
             self._pads = []
 
-    # ------------------------------------------------------------------ forward
-    def _ln16(self, x, pre, y16, mean, rstd, M, D):
-        lib.vitae_layernorm_fwd(_ptr(x), _ptr(self._param(pre + 'weight')), _ptr(self._param(pre + 'bias')), None, _ptr(y16),
-                                _ptr(mean), _ptr(rstd), M, D, self.eps, self.stream)
+    def _patch_operand(self, T, P):
+        return None, self._z16(T, P)
 
     def _block_bufs(self, B, N, D, H):
         """What one block keeps, except its input."""
-        f, z, M, heads = self._f, self._z16, B * N, self.m.num_heads
-        Mp = (M + 63) // 64 * 64
-        return {'mean1': f(M), 'rstd1': f(M), 'y1_16': z(M, Mp, D), 'qkv_16': self._e16(M, 3 * D), 'o': f(M, D),
-                'o_16': z(M, Mp, D), 'lse': f(B * heads * N), 'xmid': f(M, D), 'mean2': f(M), 'rstd2': f(M), 'y2_16': z(M, Mp, D),
-                'dgelu_16': self._e16(M, H), 'act_16': z(M, Mp, H)}
+        f, z, M = self._f, self._z16, B * N
+        return {'mean1': f(M), 'rstd1': f(M), 'y1_16': z(M, D), 'qkv_16': self._e16(M, 3 * D), 'o': f(M, D), 'o_16': z(M, D),
+                'lse': f(B * self.m.num_heads * N), 'xmid': f(M, D), 'mean2': f(M), 'rstd2': f(M), 'y2_16': z(M, D),
+                'dgelu_16': self._e16(M, H), 'act_16': z(M, H)}
 
-    def _block_run(self, q, k, x_in, B, N, D, H):
-        """One block into the buffers ``k`` -> its output."""
-        M, heads = B * N, self.m.num_heads
-        k['x_in'] = x_in
-        x_out = self._f(M, D)
-        self._ln16(x_in, q + 'norm1.', k['y1_16'], k['mean1'], k['rstd1'], M, D)
-        self._g16(k['y1_16'], q + 'attn.qkv.weight', q + 'attn.qkv.bias', M, 3 * D, D, y16=k['qkv_16'])
-        lib.vitae_sdpa_mfma_fwd_bf16in(_ptr(k['qkv_16']), _ptr(k['o']), _ptr(k['o_16']), _ptr(k['lse']), B, N, heads, self.hd, self.stream)
-        self._g16(k['o_16'], q + 'attn.proj.weight', q + 'attn.proj.bias', M, D, D, y=k['xmid'], res=x_in)
-        self._ln16(k['xmid'], q + 'norm2.', k['y2_16'], k['mean2'], k['rstd2'], M, D)
-        # aux <- bf16 GELU'(pre-activation): what the fc2 input-gradient epilogue multiplies by
-        self._g16(k['y2_16'], q + 'mlp.fc1.weight', q + 'mlp.fc1.bias', M, H, D, y16=k['act_16'],
-                  epi=EPI_GELU | EPI_AUX_BF16 | EPI_AUX_DERIV, aux=k['dgelu_16'])
-        self._g16(k['act_16'], q + 'mlp.fc2.weight', q + 'mlp.fc2.bias', M, D, H, y=x_out, res=k['xmid'])
-        return x_out
-
-    def forward_keep(self, x: torch.Tensor, needs: Dict[str, bool]):
-        """-> (features [B, D], kept): ``kept`` is what ``backward`` needs, owned by the caller."""
-        m = self.m
-        B, C, Lz, Hy, Wx, ps = self._begin(x)
-        L, D, H, P = m.patch_embed.num_patches, m.embed_dim, self.hidden, self.P
-        N, M, depth = L + 1, B * (L + 1), len(m.blocks)
-        why = act16_refusal_for(m, self.precision, in_chans=C)
-        if why:         # (the input's channel count is only known here)
-            raise VitaeError(why)
-        ids = self._workspace(B, L)
-        f, st = self._f, self.stream
-        embed, lo = self.lowest_trainable(needs, depth)
-        xc = x.detach().contiguous().float()
-        T = B * L
-        patches16, tok, cur = self._z16(T, (T + 63) // 64 * 64, P), f(T, D), f(M, D)
-        # every buffer of the call before its first launch: the blocks the backward will walk keep their own, the ones below share one set
-        blocks = {i: self._block_bufs(B, N, D, H) for i in range(min(lo, depth), depth)}
-        shared = self._block_bufs(B, N, D, H) if min(lo, depth) > 0 else None
-        self._zero_pads()
-        lib.vitae_gather_patches(_ptr(xc), _ptr(ids), None, _ptr(patches16), B, C, Lz, Hy, Wx, ps, L, st)
-        self._g16(patches16, 'patch_embed.proj.weight', 'patch_embed.proj.bias', T, D, P, y=tok)
-        lib.vitae_encoder_assemble_fwd(_ptr(tok), _ptr(self._param('cls_token')), _ptr(self._param('pos_embed')), _ptr(ids),
-                                       _ptr(cur), B, L, L, D, st)
-        for i in range(depth):
-            cur = self._block_run(f'blocks.{i}.', blocks.get(i, shared), cur, B, N, D, H)
-        pool, feat, mean, rstd = f(B, D), f(B, D), f(B), f(B)
-        if m.global_pool:
-            lib.vitae_mean_pool_tokens(_ptr(cur), _ptr(pool), B, N, D, 1, st)
-            self._ln_keep(pool, 'fc_norm.', feat, mean, rstd, B, D)
-        else:
-            pool.copy_(cur.view(B, N, D)[:, 0])
-            self._ln_keep(pool, 'norm.', feat, mean, rstd, B, D)
-        kept = {'geom': (B, L, D, H, P), 'needs': dict(needs), 'params': self.sd, 'embed': embed, 'lo': lo, 'blocks': blocks,
-                'versions': {n: p._version for n, p in self.sd.items() if not n.startswith('head.')},
-                'patches_16': patches16 if needs.get('patch_embed.proj.weight') else None, 'pool': pool, 'mean': mean, 'rstd': rstd}
-        self.stats['forwards'] += 1
-        self.stats['kept_bytes'] = (sum(t.numel() * t.element_size() for kb in blocks.values() for t in kb.values())
-                                    + sum(t.numel() * t.element_size() for t in (kept['patches_16'], pool, mean, rstd) if t is not None))
-        return feat, kept
+    def _block(self, q, k, x_in, x_out, B, N, D, H):
+        self._block16(q, k, x_in, x_out, True, EPI_AUX_BF16 | EPI_AUX_DERIV, 'dgelu_16', B, N, D, H)
 
     # ------------------------------------------------------------------ backward
     def _pair(self, grads, needs, dy16, wname, x16, M, Mpad, N, K, dx=None, dx16=None, epi=EPI_NONE, aux=None, dx_colsum=None,
               dy_colsum=None):
         """Backward of y = x W^T + b on bf16 operands, dy16 [Mpad, N]: dx / dx16 [M, K] = epi(dy16 W16) and, for a trainable weight,
         dW = dy16^T x16 in the same launch.  ``dx_colsum`` / ``dy_colsum`` (zeroed by the caller) collect column sums of dx / dy16."""
-        ws = self.buf['ws16']
-        key = ('p', M, N, K)
-        s = self._split.get(key)
-        if s is None:
-            s = lib.vitae_linear_bwd_pair_pick_split_k(M, Mpad, N, K)
-            while s > 1 and lib.vitae_gemm_glds_ws_floats(M, K, s) > ws.numel():
-                s -= 1
-            self._split[key] = s
+        ws, key = self.buf['ws16'], ('p', M, N, K)
+        s = self._split.get(key) or self._fit_split(
+            key, lambda: lib.vitae_linear_bwd_pair_pick_split_k(M, Mpad, N, K), lambda s: lib.vitae_gemm_glds_ws_floats(M, K, s),
+            ws.numel())
         dw = None
         if needs.get(wname):
             dw = grads[wname] = torch.empty_like(self._param(wname))
@@ -562,38 +548,17 @@ class HipEncoderTrainer16(HipEncoderTrainer):
         lib.vitae_linear_bwd_pair_glds(_ptr(dy16), self._bf16(wname), _ptr(x16), _ptr(dx), _ptr(dx16), _ptr(dw), None, M, Mpad, N, K,
                                        epi, _ptr(aux), _ptr(dx_colsum), _ptr(dy_colsum), 0, 0, s, ws.data_ptr(), ws.numel(), self.stream)
 
-    def _ln_bwd16(self, grads, needs, dy, x, pre, mean, rstd, dx, dx16, dx_colsum, M, D):
-        dw, db = self._z(D), self._z(D)             # the launcher adds its column partials
-        lib.vitae_layernorm_bwd(_ptr(dy), _ptr(x), _ptr(self._param(pre + 'weight')), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dw),
-                                _ptr(db), _ptr(dx16), _ptr(dx_colsum), M, D, 1, self.stream)
-        if needs.get(pre + 'weight'):
-            grads[pre + 'weight'] = dw
-        if needs.get(pre + 'bias'):
-            grads[pre + 'bias'] = db
-
     def backward(self, kept, dfeat: torch.Tensor) -> Dict[str, torch.Tensor]:
         """d loss / d features [B, D] -> {parameter name: gradient} for the trainable parameters of the encoder."""
+        grads, dpool = self._backward_head(kept, dfeat)
+        if dpool is None:
+            return grads
         m = self.m
         B, L, D, H, P = kept['geom']
         N, M, depth, heads = L + 1, B * (L + 1), len(m.blocks), m.num_heads
-        Mp = (M + 63) // 64 * 64
-        self.device = dfeat.device
-        self.stream = torch.cuda.current_stream(dfeat.device).cuda_stream
-        self.sd = kept['params']
-        stale = [n for n, v in kept['versions'].items() if self.sd[n]._version != v]
-        if stale:       # the backward reads the bf16 weight copies again (keyed by version): they must be the ones the forward used
-            raise VitaeError(f'parameters were modified in place between forward and backward: {stale[:3]} ...')
-        self._workspace(B, L)
+        Mp = _pad64(M)
         needs, f, st = kept['needs'], self._f, self.stream
-        grads: Dict[str, torch.Tensor] = {}
-        dfeat = dfeat.contiguous().float()
-        dpool = f(B, D)
-        self._ln_bwd(grads, needs, dfeat, kept['pool'], 'fc_norm.' if m.global_pool else 'norm.', kept['mean'], kept['rstd'],
-                     dpool, B, D, 0)
-        self.stats['backwards'] += 1
         embed, lo = kept['embed'], kept['lo']
-        if not embed and lo >= depth:
-            return grads
 
         def bias(name):     # a bias gradient that launches ADD column sums to; None for a frozen bias
             if needs.get(name):
@@ -606,11 +571,10 @@ class HipEncoderTrainer16(HipEncoderTrainer):
         fc2_b = bias(f'blocks.{depth - 1}.mlp.fc2.bias') if depth else None
         lib.vitae_token_select_bwd16(_ptr(dpool), _ptr(dx), _ptr(dx16), _ptr(fc2_b), B, N, Mp, D, 1 if m.global_pool else 0, st)
         T = B * L
-        Tp = (T + 63) // 64 * 64
         if depth > lo:
-            dh16, dqkv16 = self._z16(M, Mp, H), self._z16(M, Mp, 3 * D)
+            dh16, dqkv16 = self._z16(M, H), self._z16(M, 3 * D)
             dy, do, delta = f(M, D), f(M, D), f(B * heads * N)
-        dtok16 = self._z16(T, Tp, D) if (embed and needs.get('patch_embed.proj.weight')) else None
+        dtok16 = self._z16(T, D) if (embed and needs.get('patch_embed.proj.weight')) else None
         self._zero_pads()
         for i in range(depth - 1, lo - 1, -1):
             q, k = f'blocks.{i}.', kept['blocks'][i]
@@ -620,7 +584,7 @@ class HipEncoderTrainer16(HipEncoderTrainer):
             self._pair(grads, needs, dx16, q + 'mlp.fc2.weight', k['act_16'], M, Mp, D, H, dx16=dh16,
                        epi=EPI_DGELU | EPI_AUX_BF16 | EPI_AUX_DERIV, aux=k['dgelu_16'], dx_colsum=None if by_w else fc1_b)
             self._pair(grads, needs, dh16, q + 'mlp.fc1.weight', k['y2_16'], M, Mp, H, D, dx=dy, dy_colsum=fc1_b if by_w else None)
-            self._ln_bwd16(grads, needs, dy, k['xmid'], q + 'norm2.', k['mean2'], k['rstd2'], dx, dx16, bias(q + 'attn.proj.bias'), M, D)
+            self._ln_bwd(grads, needs, dy, k['xmid'], q + 'norm2.', k['mean2'], k['rstd2'], dx, M, D, 1, dx16, bias(q + 'attn.proj.bias'))
             self._pair(grads, needs, dx16, q + 'attn.proj.weight', k['o_16'], M, Mp, D, D, dx=do)
             # qkv's bias gradient colsum(dqkv): beside its weight gradient, or collected by the attention backward for a frozen weight
             qkv_b = bias(q + 'attn.qkv.bias')
@@ -630,8 +594,8 @@ class HipEncoderTrainer16(HipEncoderTrainer):
             self._pair(grads, needs, dqkv16, q + 'attn.qkv.weight', k['y1_16'], M, Mp, 3 * D, D, dx=dy, dy_colsum=qkv_b if by_w else None)
             # norm1 leaves the output gradient of block i - 1: fp32, bf16, and its column sums = that block's fc2 bias gradient
             below = i > lo
-            self._ln_bwd16(grads, needs, dy, k['x_in'], q + 'norm1.', k['mean1'], k['rstd1'], dx, dx16 if below else None,
-                           bias(f'blocks.{i - 1}.mlp.fc2.bias') if below else None, M, D)
+            self._ln_bwd(grads, needs, dy, k['x_in'], q + 'norm1.', k['mean1'], k['rstd1'], dx, M, D, 1, dx16 if below else None,
+                         bias(f'blocks.{i - 1}.mlp.fc2.bias') if below else None)
         if embed:
             want_w, want_b = needs.get('patch_embed.proj.weight'), needs.get('patch_embed.proj.bias')
             pos = self._param('pos_embed')
@@ -647,6 +611,6 @@ class HipEncoderTrainer16(HipEncoderTrainer):
             if want_w:
                 # dW[D, P] = dtok16^T @ patches16 (both row-contiguous bf16, reduced over the padded token count)
                 dw = grads['patch_embed.proj.weight'] = torch.empty_like(self._param('patch_embed.proj.weight'))
-                lib.vitae_gemm_glds(0, 0, _ptr(dtok16), D, _ptr(kept['patches_16']), P, _ptr(dw), P, None, P, D, P, Tp, None, None, 0,
+                lib.vitae_gemm_glds(0, 0, _ptr(dtok16), D, _ptr(kept['patches']), P, _ptr(dw), P, None, P, D, P, _pad64(T), None, None, 0,
                                     EPI_NONE, None, 0, 0, 1, None, None, st)
         return {n: g for n, g in grads.items() if g is not None}
