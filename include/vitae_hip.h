@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define VITAE_ABI_VERSION 53
+#define VITAE_ABI_VERSION 54
 
 /* matrix-core arithmetic of the dense contractions */
 #define VITAE_PREC_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32 (the reference's precision, autocast off at utils/train_one_epoch.py:50) */
@@ -573,6 +573,40 @@ int vitae_opt_tail(float* params, const void* grads, int grads_bf16, void* exp_a
 int vitae_step_prologue(float* hp, const float* hp_ring, int ring_slots, const long long* step_seq, float* noise, long n_noise,
                         long long seed, double* acc, void* zero_ptr, long zero_bytes, void* stream);
 int vitae_step_epilogue(long long* step_seq, void* stream);
+
+/* ---- multi-tensor AdamW (ABI 54): fine-tuning's ~150 separate parameters in up to VITAE_MULTI_MAX_GROUPS layer-decay groups
+ * (utils/lr_decay.py param_groups_lrd), the global norm of utils/misc.py:280-292 and clip_grad_norm_ — two launches per step.
+ *   table   n_entries entries of VITAE_MULTI_ENTRY_WORDS 64-bit words: p, g, exp_avg, exp_avg_sq (device addresses of
+ *           contiguous fp32), the element count, the group index.  A tensor whose four addresses are all 16-byte aligned is
+ *           streamed 16 bytes at a time (its last n % 4 elements one by one); any other tensor element by element.
+ *   chunks  n_chunks pairs of ints (tensor index, chunk index): chunk k of a tensor is its elements [k * chunk, min(n, (k + 1) *
+ *           chunk)).  The caller lists every chunk of every tensor once; a persistent grid of one workgroup per CU walks the list.
+ *           chunk: a positive multiple of 4; VITAE_MULTI_CHUNK is what optim.MultiTensorAdamW uses (LABNOTES: the values timed).
+ * Both arrays are passed twice: *_host is read by the launcher, which judges the whole call before its first launch, *_dev is the
+ * device copy the kernels read (the caller enqueued that copy on `stream`).  Refusals, nothing written: VITAE_ERR_INVALID_ARG for a
+ * NULL array / acc / state / norm_out / group_lr_dev / group_wd_dev, a NULL address in an entry (vitae_grad_sqnorm_multi only needs g), a
+ * negative count, n_groups outside [1, VITAE_MULTI_MAX_GROUPS], an entry's group outside [0, n_groups), a chunk pair outside its
+ * tensor, chunk <= 0 or chunk % 4.  n_entries == 0 or n_chunks == 0: success, nothing is launched. */
+#define VITAE_MULTI_MAX_GROUPS 64
+#define VITAE_MULTI_CHUNK 16384
+#define VITAE_MULTI_ENTRY_WORDS 6
+/* device-resident float[VITAE_MULTI_STATE_COUNT] of one optimiser (floats holding integers, as hp[VITAE_HP_STEP]) */
+#define VITAE_MULTI_STATE_STEP 0     /* AdamW steps applied so far: the bias corrections use this + 1 */
+#define VITAE_MULTI_STATE_SKIPPED 1  /* steps skipped because the gradient norm was not finite */
+#define VITAE_MULTI_STATE_COUNT 2
+/* acc (double[VITAE_ACC_COUNT], zero on entry): the VITAE_ACC_SQ_* spread slots += the squares of every listed gradient, in double */
+int vitae_grad_sqnorm_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                            const int* chunks_dev, long n_chunks, long chunk, double* acc, void* stream);
+/* AdamW over every listed tensor in one launch.  Every workgroup forms norm = sqrt(acc[VITAE_ACC_GRADSQ] + the spread slots) itself;
+ * not finite: nothing is written to any tensor.  Else gs = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1 (clip_grad_norm_'s
+ * factor) multiplies every gradient as it is read (g itself is not rewritten) and each tensor is stepped with its group's
+ * group_lr_dev[group], group_wd_dev[group] (device arrays of n_groups floats, sent with the table) and the call's betas / eps; bias
+ * corrections from state[VITAE_MULTI_STATE_STEP] + 1.  The last workgroup to finish (acc[VITAE_ACC_TICKET_B]) writes norm_out[0] =
+ * norm, bumps state[STEP] (state[SKIPPED] when the norm was not finite) and leaves the ticket, acc[VITAE_ACC_GRADSQ] and the
+ * spread slots zero for the next step. */
+int vitae_adamw_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                      const int* chunks_dev, long n_chunks, long chunk, const float* group_lr_dev, const float* group_wd_dev, int n_groups,
+                      double beta1, double beta2, double eps, double max_norm, float* state, double* acc, float* norm_out, void* stream);
 
 #ifdef __cplusplus
 }

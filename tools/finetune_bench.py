@@ -15,7 +15,14 @@ evaluate() in volumes/s (batch 16, 4 batches, bf16 and fp32).
 activations='bf16')``) against the default bf16 route, timed alternating A / B on two models in this process, with the inference
 forward of the same model beside them; ``--batch B`` picks one batch size (default 4 and 16).
 
-    python tools/finetune_bench.py step --activations bf16 [--batch 4]"""
+    python tools/finetune_bench.py step --activations bf16 [--batch 4]
+
+``optimizer`` (only when named): the whole step of the bf16-activation route through ``NativeScalerWithGradNormCount`` over layer-decay
+groups with (a) ``torch.optim.AdamW``, (b) ``torch.optim.AdamW(fused=True)`` where this torch build accepts it, (c)
+``optim.MultiTensorAdamW``, the three in turns inside this process, with and without ``clip_grad``; then the optimiser part alone
+(norm [+ clipping] + step on the gradients of the last backward) and ``MultiTensorAdamW`` alone at several chunk lengths.
+
+    python tools/finetune_bench.py optimizer [--batch 4]"""
 import os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -39,19 +46,20 @@ def _option(name):
 
 
 def _usage(msg):
-    sys.exit(f'finetune_bench.py: {msg}\nusage: finetune_bench.py [step] [mixup] [criterion] [evaluate] | step --activations bf16 [--batch B]')
+    sys.exit(f'finetune_bench.py: {msg}\nusage: finetune_bench.py [step] [mixup] [criterion] [evaluate] | step --activations bf16 [--batch B] | optimizer [--batch B]')
 
 
 ACTIVATIONS, BATCH = _option('--activations'), _option('--batch')
 ROWS = ARGV or ['step', 'mixup', 'criterion', 'evaluate']
-if [r for r in ROWS if r not in ('step', 'mixup', 'criterion', 'evaluate')]:
-    _usage(f'unknown argument(s) {[r for r in ROWS if r not in ("step", "mixup", "criterion", "evaluate")]}')
+KNOWN = ('step', 'mixup', 'criterion', 'evaluate', 'optimizer')
+if [r for r in ROWS if r not in KNOWN]:
+    _usage(f'unknown argument(s) {[r for r in ROWS if r not in KNOWN]}')
 if ACTIVATIONS is not None and ACTIVATIONS != 'bf16':
     _usage(f"--activations takes 'bf16' (got {ACTIVATIONS!r})")
-if (ACTIVATIONS or BATCH) and ROWS != ['step']:
+if ACTIVATIONS and ROWS != ['step'] or BATCH and ROWS not in (['step'], ['optimizer']):
     _usage('--activations / --batch go with the step row alone: finetune_bench.py step --activations bf16 [--batch B]')
-if BATCH is not None and (not ACTIVATIONS or not BATCH.isdigit() or int(BATCH) < 1):
-    _usage('--batch takes a positive integer and goes with --activations')
+if BATCH is not None and (not (ACTIVATIONS or ROWS == ['optimizer']) or not BATCH.isdigit() or int(BATCH) < 1):
+    _usage('--batch takes a positive integer and goes with --activations or with the optimizer row')
 
 
 def timed(fn):
@@ -68,20 +76,20 @@ def timed(fn):
 
 
 
-def timed_ab(fa, fb):
-    """Medians (and min .. max) of two callables timed in turns: A, B, A, B ... so drift of the clocks hits both alike."""
+def timed_ab(*fns):
+    """Medians (and min .. max) of two or more callables timed in turns: A, B, A, B ... so drift of the clocks hits all alike."""
     for _ in range(WARMUP):
-        fa()
-        fb()
-    ta, tb = [], []
+        for fn in fns:
+            fn()
+    tss = [[] for _ in fns]
     for _ in range(ITERS):
-        for fn, ts in ((fa, ta), (fb, tb)):
+        for fn, ts in zip(fns, tss):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             fn()
             torch.cuda.synchronize()
             ts.append((time.perf_counter() - t0) * 1e3)
-    return [(statistics.median(ts), min(ts), max(ts)) for ts in (ta, tb)]
+    return [(statistics.median(ts), min(ts), max(ts)) for ts in tss]
 
 
 def mixup_rows():
@@ -195,6 +203,90 @@ def act16_rows():
         del fns, models, x
 
 
+def optimizer_rows():
+    """torch.optim.AdamW, its fused form and MultiTensorAdamW in turns: the whole step through the scaler, then the optimiser part alone."""
+    from vit_ae_plus_plus_amd.optim import MultiTensorAdamW
+    from vit_ae_plus_plus_amd.utils.misc import NativeScalerWithGradNormCount, get_grad_norm_
+    LR = 1e-5        # several hundred steps on one batch: small enough that no route ever sees a non-finite gradient (checked below)
+    makers = [('torch.optim.AdamW', lambda g: torch.optim.AdamW(g, lr=LR))]
+    try:
+        probe = torch.nn.Parameter(torch.zeros(4, device='cuda'))
+        probe.grad = torch.zeros_like(probe)
+        torch.optim.AdamW([probe], fused=True).step()
+        makers.append(('torch.optim.AdamW(fused=True)', lambda g: torch.optim.AdamW(g, lr=LR, fused=True)))
+    except Exception as e:      # this build has no fused AdamW for the device: the row is left out, and said so
+        print(f'optimizer: torch.optim.AdamW(fused=True) is not available here ({type(e).__name__}: {e})', flush=True)
+    makers.append(('MultiTensorAdamW', lambda g: MultiTensorAdamW(g, lr=LR)))
+    scaler = NativeScalerWithGradNormCount()
+    for B in ([int(BATCH)] if BATCH else [4, 16]):
+        x = torch.randn(B, 4, 96, 96, 96, device='cuda')
+        y = torch.randint(0, 2, (B,), device='cuda')
+        crit = torch.nn.CrossEntropyLoss()
+        runs = []
+        for name, make in makers:
+            m = VisionTransformer3D(volume_size=96, patch_size=16, in_chans=4, num_classes=2, global_pool=True, precision='bf16',
+                                    activations='bf16', drop_path_rate=0.1).cuda().train()
+            torch.nn.init.normal_(m.head.weight, std=0.02)
+            runs.append((name, m, make(param_groups_lrd(m, 0.05, m.no_weight_decay(), 0.75))))
+        n_params = sum(p.numel() for p in runs[0][1].parameters())
+        print(f'optimizer B={B}: {n_params / 1e6:.1f} M parameters in {len(list(runs[0][1].parameters()))} tensors, '
+              f'{len(runs[0][2].param_groups)} groups', flush=True)
+        medians = {}
+        for clip in (None, 1.0):
+            def whole(m, opt):
+                def f():
+                    opt.zero_grad(set_to_none=True)
+                    scaler(crit(m(x), y), opt, clip_grad=clip, parameters=m.parameters())
+                return f
+
+            def alone(m, opt):      # on the gradients the last whole step left behind
+                params = list(m.parameters())
+                if hasattr(opt, 'norm_clip_step'):
+                    return lambda: opt.norm_clip_step(clip)
+
+                def f():
+                    if clip is not None:
+                        torch.nn.utils.clip_grad_norm_(params, clip)
+                    else:
+                        get_grad_norm_(params)
+                    opt.step()
+                return f
+
+            ws = timed_ab(*[whole(m, opt) for _, m, opt in runs])
+            os_ = timed_ab(*[alone(m, opt) for _, m, opt in runs])
+            for (name, _, _), w, o in zip(runs, ws, os_):
+                medians[(name, clip)] = w
+                print(f'optimizer B={B} clip_grad={clip!s:4s} {name:30s}: whole step {w[0]:.3f} ms ({w[1]:.3f} .. {w[2]:.3f}), optimiser alone '
+                      f'{o[0]:.3f} ms ({o[1]:.3f} .. {o[2]:.3f}) = {28 * n_params / o[0] / 1e9:.2f} TB/s at 28 B per parameter', flush=True)
+            a, c = medians[(makers[0][0], clip)], medians[('MultiTensorAdamW', clip)]
+            spread = max(a[2] - a[1], c[2] - c[1])
+            print(f'optimizer B={B} clip_grad={clip}: MultiTensorAdamW / torch.optim.AdamW = {c[0] / a[0]:.3f} (whole step; gain {a[0] - c[0]:.3f} ms, '
+                  f'larger min .. max spread {spread:.3f} ms)', flush=True)
+        _, m, opt = runs[-1]
+        lengths = (4096, 8192, 16384, 32768, 65536)
+
+        REPS = 8     # calls issued back to back per sample: the host prepares call k + 1 while the device runs call k
+
+        def with_chunk(c, reps):
+            def f():
+                opt._chunk = c
+                for _ in range(reps):
+                    opt.norm_clip_step(None)
+            return f
+
+        one = timed_ab(*[with_chunk(c, 1) for c in lengths])
+        many = timed_ab(*[with_chunk(c, REPS) for c in lengths])
+        for c, t, q in zip(lengths, one, many):
+            print(f'optimizer B={B} MultiTensorAdamW alone, chunk {c:6d}: one call {t[0]:.3f} ms ({t[1]:.3f} .. {t[2]:.3f}); {REPS} calls back to '
+                  f'back {q[0] / REPS:.3f} ms each ({q[1] / REPS:.3f} .. {q[2] / REPS:.3f}) = {28 * n_params / q[0] * REPS / 1e9:.2f} TB/s', flush=True)
+        finite = all(bool(torch.isfinite(p).all()) for p in m.parameters())
+        print(f'optimizer B={B}: MultiTensorAdamW applied {opt.applied_steps()} steps, skipped {opt.skipped_steps()}; parameters finite: {finite}',
+              flush=True)
+        del runs, m, opt, x
+
+
+if 'optimizer' in ROWS:
+    optimizer_rows()
 if 'step' in ROWS and ACTIVATIONS:
     act16_rows()
 elif 'step' in ROWS:

@@ -314,6 +314,130 @@ __global__ void step_epilogue_kernel(long long* __restrict__ seq) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *seq += 1;
 }
 
+// ---- multi-tensor AdamW (ABI 54): fine-tuning's separate parameters in layer-decay groups, two launches per step
+struct MultiEntry { float* p; const float* g; float* m; float* v; long long n; long long group; };
+static_assert(sizeof(MultiEntry) == 8 * VITAE_MULTI_ENTRY_WORDS, "table entry layout (vitae_hip.h)");
+
+// Squares are formed and summed in double (a product of two floats is exact there): what is left of the norm's error is the final
+// rounding to fp32.  Read-only, so four workgroups per CU keep enough bytes in flight without unrolling.
+__global__ __launch_bounds__(256) void grad_sqnorm_multi_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks,
+                                                                long n_chunks, long chunk, double* __restrict__ acc) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const MultiEntry e = table[chunks[2 * c]];
+        const long off = (long)chunks[2 * c + 1] * chunk;
+        const float* g = e.g + off;
+        const long len = e.n - off < chunk ? e.n - off : chunk;
+        long done = 0;
+        if (!((uintptr_t)g & 15)) {
+            const long n4 = len / 4;
+            for (long i = threadIdx.x; i < n4; i += 256) {
+                const f32x4 v = grad4<float>(g, i);
+                s += (double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2] + (double)v[3] * v[3];
+            }
+            done = n4 * 4;
+        }
+        for (long i = done + threadIdx.x; i < len; i += 256) s += (double)g[i] * g[i];
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) s += __shfl_xor(s, d, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(gradsq_slot(acc), red[0] + red[1] + red[2] + red[3]);
+}
+
+// adamw_kernel's data path (U independent 16-byte groups per thread, non-temporal moments and gradients) over one chunk at a time
+template <int U>
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks, long n_chunks,
+                                                          long chunk, const float* __restrict__ group_lr,
+                                                          const float* __restrict__ group_wd, float omb1, float b2, float omb2, float eps,
+                                                          float max_norm, float* __restrict__ state, double* __restrict__ acc,
+                                                          float* __restrict__ norm_out) {
+    __shared__ int last;
+    // the norm straight from the accumulator, as adamw_kernel's gacc gate: every wave sums the spread slots itself
+    double q = acc[VITAE_ACC_SQ_BASE + (threadIdx.x & 63) * VITAE_ACC_SQ_STRIDE];
+    if ((threadIdx.x & 63) == 0) q += acc[VITAE_ACC_GRADSQ];
+#pragma unroll
+    for (int d = 32; d; d >>= 1) q += __shfl_xor(q, d, 64);
+    const float gn = (float)sqrt(q);
+    const bool finite = gn == gn && fabsf(gn) != INFINITY;
+    const float t = state[VITAE_MULTI_STATE_STEP] + 1.f;
+    if (finite) {
+        float bc1, bc2;
+        device_bias_corrections(omb1, omb2, t, bc1, bc2);
+        const float sq_bc2 = sqrtf(bc2);
+        const float gs = max_norm > 0.f ? fminf(1.f, max_norm / (gn + 1e-6f)) : 1.f;      // torch.nn.utils.clip_grad_norm_
+        for (long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+            const MultiEntry e = table[chunks[2 * c]];
+            const long off = (long)chunks[2 * c + 1] * chunk;
+            const long len = e.n - off < chunk ? e.n - off : chunk;
+            const float lr = group_lr[e.group];
+            const float decay = adamw_decay(lr, group_wd[e.group]), step = lr / bc1;
+            float* p = e.p + off;
+            const float* g = e.g + off;
+            float *m = e.m + off, *v = e.v + off;
+            long done = 0;
+            // chunk and off are multiples of 4: the chunk is 16-byte aligned exactly when the tensor's base addresses are
+            if (!(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15)) {
+                const long n4 = len / 4;
+                f32x4* p4 = reinterpret_cast<f32x4*>(p);
+                for (long i0 = threadIdx.x; i0 < n4; i0 += U * 256) {
+                    long idx[U];
+                    bool live[U];
+                    f32x4 pp[U], mm[U], vv[U], gg[U];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        live[u] = i0 + u * 256 < n4;
+                        idx[u] = live[u] ? i0 + u * 256 : i0;
+                        pp[u] = p4[idx[u]];
+                        mm[u] = state4_ld<float>(m, idx[u]);
+                        vv[u] = state4_ld<float>(v, idx[u]);
+                        gg[u] = grad4<float>(g, idx[u]);
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        if (!live[u]) break;
+                        const long i = idx[u];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            float pe = pp[u][k], me = mm[u][k], ve = vv[u][k];
+                            adamw_element(pe, me, ve, gg[u][k], gs, decay, omb1, b2, omb2, step, sq_bc2, eps);
+                            pp[u][k] = pe; mm[u][k] = me; vv[u][k] = ve;
+                        }
+                        p4[i] = pp[u];
+                        state4_st<float>(m, i, mm[u]);
+                        state4_st<float>(v, i, vv[u]);
+                    }
+                }
+                done = n4 * 4;
+            }
+            for (long i = done + threadIdx.x; i < len; i += 256) {
+                float pe = p[i], me = m[i], ve = v[i];
+                adamw_element(pe, me, ve, g[i], gs, decay, omb1, b2, omb2, step, sq_bc2, eps);
+                p[i] = pe; m[i] = me; v[i] = ve;
+            }
+        }
+    }
+    // the LAST workgroup to get here (every one has read the accumulator and state[STEP] by then) publishes the norm, counts the step
+    // and leaves the accumulator as it found it before the norm pass: zero
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        last = atomicAdd(reinterpret_cast<int*>(acc + VITAE_ACC_TICKET_B), 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (last && threadIdx.x < 64) {
+        acc[VITAE_ACC_SQ_BASE + threadIdx.x * VITAE_ACC_SQ_STRIDE] = 0.0;
+        if (threadIdx.x == 0) {
+            acc[VITAE_ACC_GRADSQ] = 0.0;
+            acc[VITAE_ACC_TICKET_B] = 0.0;
+            norm_out[0] = gn;
+            state[finite ? VITAE_MULTI_STATE_STEP : VITAE_MULTI_STATE_SKIPPED] += 1.f;
+        }
+    }
+}
+
 }  // namespace
 
 template <typename G>
@@ -462,6 +586,51 @@ extern "C" int vitae_step_prologue(float* hp, const float* hp_ring, int ring_slo
 extern "C" int vitae_step_epilogue(long long* step_seq, void* stream) {
     if (!step_seq) return VITAE_ERR_INVALID_ARG;
     hipLaunchKernelGGL(step_epilogue_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_seq);
+    return vitae_launch_status();
+}
+
+// ---- multi-tensor AdamW: the whole call is judged on the host copies before the first launch
+static int multi_check(const long long* table, long n_entries, const int* chunks, long n_chunks, long chunk, int n_groups, bool all_ptrs) {
+    if (n_entries < 0 || n_chunks < 0 || chunk <= 0 || (chunk & 3)) return VITAE_ERR_INVALID_ARG;
+    if (n_entries == 0 || n_chunks == 0) return VITAE_OK;
+    if (!table || !chunks) return VITAE_ERR_INVALID_ARG;
+    for (long t = 0; t < n_entries; ++t) {
+        const long long* e = table + t * VITAE_MULTI_ENTRY_WORDS;
+        if (!e[1] || e[4] < 0) return VITAE_ERR_INVALID_ARG;
+        if (all_ptrs && (!e[0] || !e[2] || !e[3] || e[5] < 0 || e[5] >= n_groups)) return VITAE_ERR_INVALID_ARG;
+    }
+    for (long c = 0; c < n_chunks; ++c) {
+        const long t = chunks[2 * c], k = chunks[2 * c + 1];
+        if (t < 0 || t >= n_entries || k < 0 || (long long)k * chunk >= table[t * VITAE_MULTI_ENTRY_WORDS + 4]) return VITAE_ERR_INVALID_ARG;
+    }
+    return VITAE_OK;
+}
+
+extern "C" int vitae_grad_sqnorm_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                                       const int* chunks_dev, long n_chunks, long chunk, double* acc, void* stream) {
+    const int rc = multi_check(table_host, n_entries, chunks_host, n_chunks, chunk, 0, false);
+    if (rc != VITAE_OK || n_entries == 0 || n_chunks == 0) return rc;
+    if (!table_dev || !chunks_dev || !acc) return VITAE_ERR_INVALID_ARG;
+    const long blocks = n_chunks < 1024 ? n_chunks : 1024;
+    hipLaunchKernelGGL(grad_sqnorm_multi_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const MultiEntry*>(table_dev), chunks_dev, n_chunks, chunk, acc);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_adamw_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                                 const int* chunks_dev, long n_chunks, long chunk, const float* group_lr_dev, const float* group_wd_dev, int n_groups,
+                                 double beta1, double beta2, double eps, double max_norm, float* state, double* acc, float* norm_out,
+                                 void* stream) {
+    if (n_groups < 1 || n_groups > VITAE_MULTI_MAX_GROUPS || !group_lr_dev || !group_wd_dev) return VITAE_ERR_INVALID_ARG;
+    const int rc = multi_check(table_host, n_entries, chunks_host, n_chunks, chunk, n_groups, true);
+    if (rc != VITAE_OK || n_entries == 0 || n_chunks == 0) return rc;
+    if (!table_dev || !chunks_dev || !state || !acc || !norm_out) return VITAE_ERR_INVALID_ARG;
+    // one 256-thread workgroup per CU, as adamw_launch (and for its reasons); the chunk list deals the tensors out evenly
+    const long blocks = n_chunks < 256 ? n_chunks : 256;
+    // 1 - beta from the host's doubles: what a negative VITAE_HP_BC slot carries for adamw_kernel
+    hipLaunchKernelGGL(adamw_multi_kernel<8>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const MultiEntry*>(table_dev), chunks_dev, n_chunks, chunk, group_lr_dev, group_wd_dev, (float)(1.0 - beta1), (float)beta2,
+                       (float)(1.0 - beta2), (float)eps, (float)max_norm, state, acc, norm_out);
     return vitae_launch_status();
 }
 

@@ -280,6 +280,12 @@ class NativeScalerWithGradNormCount:
         engine = getattr(optimizer, 'engine', None)
         if self.grad_sync is not None:
             self.grad_sync()
+        if hasattr(optimizer, 'norm_clip_step'):
+            # optim.MultiTensorAdamW: norm, clipping and the step in its own two launches.  Only when the norm it forms is the
+            # one asked for: a gradient among `parameters` that the optimiser does not own takes the generic path below.
+            owned = {id(p) for g in optimizer.param_groups for p in g['params']}
+            if all(id(p) in owned for p in params if p.grad is not None):
+                return optimizer.norm_clip_step(clip_grad)
         if clip_grad is not None:
             norm = torch.nn.utils.clip_grad_norm_(params, clip_grad)
         elif engine is not None:
