@@ -212,9 +212,13 @@ __device__ __forceinline__ f32x16 bcast16(float x) {
 }
 
 // max over the two lanes that hold the same query (lane, lane ^ 32)
+// v_permlane32_swap exchanges lanes 32-63 of its first register with lanes 0-31 of its second: afterwards a and b hold the lane's own
+// value and its partner's.  It is asm because the second result of __builtin_amdgcn_permlane32_swap is miscompiled on this toolchain
+// (the fmaxf of the two results is dropped); the s_nops cover the VALU hazards the compiler cannot see around an asm block.
 __device__ __forceinline__ float half_pair_max(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, x), __builtin_bit_cast(unsigned, x), false, false);
-    return fmaxf(__builtin_bit_cast(float, r[0]), __builtin_bit_cast(float, r[1]));
+    float a = x, b = x;
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
+    return fmaxf(a, b);
 }
 
 __device__ __forceinline__ float max16(const f32x16& s) {
@@ -319,7 +323,8 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const QT* __restrict
 #pragma unroll
                     for (int qb = 0; qb < QB; ++qb) {
                         const float delta = first ? tm[qb] : fmaxf(tm[qb], 0.f);
-                        const float corr = __builtin_amdgcn_exp2f(-delta);
+                        // (nothing is accumulated before the first step: exp2(-delta) of a maximum below -128 would make 0 * inf of it)
+                        const float corr = first ? 1.f : __builtin_amdgcn_exp2f(-delta);
                         m[qb] += delta;
                         lsum[qb] *= corr;
                         negm[qb] = bcast16(-m[qb]);
