@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define VITAE_ABI_VERSION 54
+#define VITAE_ABI_VERSION 55
 
 /* matrix-core arithmetic of the dense contractions */
 #define VITAE_PREC_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32 (the reference's precision, autocast off at utils/train_one_epoch.py:50) */
@@ -226,6 +226,10 @@ int vitae_linear_bwd_weight(int prec, const float* dy, const float* x, float* dw
                             int accumulate, int split_k, float* ws, void* stream);
 /* out[n] += sum_m dy[m*ld + n]  (bias gradients) */
 int vitae_colsum_accum(const float* dy, long ld, float* out, int M, int N, void* stream);
+/* (ABI 55) the same without atomics, two launches: slabs of 32 rows leave their column partials in ws (vitae_colsum_ordered_ws_floats(M, N)
+ * floats), then out[n] += their sum in slab order: bitwise reproducible.  What MoCo's base encoder trains its fp32 route with. */
+long vitae_colsum_ordered_ws_floats(int M, int N);
+int vitae_colsum_ordered(const float* dy, long ld, float* out, float* ws, int M, int N, void* stream);
 
 /* ---- LayerNorm (partial(nn.LayerNorm, eps=1e-6): model/vit_autoenc.py:292,300,308; used at
  * model/vit.py:132,135,142-143, model/vit_autoenc.py:36,51,175,195) ------------------------------ */
@@ -246,6 +250,11 @@ int vitae_layernorm_bwd(const float* dy, const float* x, const float* w, const f
 int vitae_layernorm_bwd_part_records(int M);
 int vitae_layernorm_bwd_part(const float* dy, const float* x, const float* w, const float* mean, const float* rstd,
                              float* dx, float* part, void* dx_bf16, int M, int D, int dx_accumulate, void* stream);
+/* (ABI 55) the same record form for any other D <= 768 with D % 4 == 0 (the generic rows kernel): ceil(M / VITAE_LN_PART_ANY_ROWS)
+ * records; part 16-byte aligned.  What MoCo's base encoder trains with: its LayerNorm parameter gradients reproduce bit for bit. */
+#define VITAE_LN_PART_ANY_ROWS 8
+int vitae_layernorm_bwd_part_any(const float* dy, const float* x, const float* w, const float* mean, const float* rstd,
+                                 float* dx, float* part, void* dx_bf16, int M, int D, int dx_accumulate, void* stream);
 int vitae_ln_grad_reduce(int n, const float* const* part, float* const* dw, float* const* db, float* const* dx_colsum,
                          const int* records, const int* D, void* stream);
 
@@ -519,6 +528,16 @@ int vitae_bn1d_relu_fwd_split(const float* x, const float* w, const float* b, fl
 int vitae_bn1d_relu_bwd_split(const float* dy, const float* x, const float* y, const float* w, const float* save_mean,
                               const float* save_rstd, float* dx, void* dx_bf16, float* dw_accum, float* db_accum, int R, int D,
                               float* ws, void* stream);
+/* Plain BatchNorm1d (ABI 55; the projector / predictor MLPs of other_baselines/mocov3/moco/builder.py): the three single-launch forms
+ * above without the ReLU — the same kernels, instantiated without it; same D % 4 and 16-byte rules.  w == NULL and b == NULL (both or
+ * neither) mean affine=False.  bwd: dy is the gradient of y itself; dw / db (both or neither; accumulated into, as above) need w. */
+int vitae_bn1d_fwd(const float* x, const float* w, const float* b, float* y, void* y_bf16, float* save_mean, float* save_rstd,
+                   float* running_mean, float* running_var, long long* num_batches_tracked, int R, int D, float eps, float momentum,
+                   void* stream);
+int vitae_bn1d_eval(const float* x, const float* w, const float* b, const float* running_mean, const float* running_var, float* y,
+                    int R, int D, float eps, void* stream);
+int vitae_bn1d_bwd(const float* dy, const float* x, const float* w, const float* save_mean, const float* save_rstd, float* dx,
+                   void* dx_bf16, float* dw_accum, float* db_accum, int R, int D, void* stream);
 /* contr = contr_w * (-(mean cos(p1,z2) + mean cos(p2,z1))/2)  (utils/train_one_epoch.py:113-114); cos(p, z) = <p, z> / (max(|p|, 1e-8)
  * max(|z|, 1e-8)) (nn.CosineSimilarity).  The backward differentiates exactly that: a row with |p| < 1e-8 gets coef z / (1e-8 max(|z|, 1e-8))
  * without the - cos p / |p|^2 term (ABI 51; the clamped norm is a constant) */
@@ -607,6 +626,38 @@ int vitae_grad_sqnorm_multi(const long long* table_host, const long long* table_
 int vitae_adamw_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
                       const int* chunks_dev, long n_chunks, long chunk, const float* group_lr_dev, const float* group_wd_dev, int n_groups,
                       double beta1, double beta2, double eps, double max_norm, float* state, double* acc, float* norm_out, void* stream);
+
+/* ---- MoCo v3 (ABI 55, csrc/moco.hip): other_baselines/mocov3/moco/builder.py and optimizer.py around the encoder.
+ * vitae_ema_multi / vitae_lars_multi walk the table + chunk list of the multi-tensor AdamW above (same layout, same host / device
+ * pairs, same refusals, nothing written on a refusal; n_entries == 0 or n_chunks == 0: success, nothing launched).
+ *
+ * vitae_ema_multi (builder.py:60-61), one launch: entry = (pm, pb, unused, unused, n, unused); pm[i] <- pm[i] * (float)m +
+ * pb[i] * (float)(1. - m): two fp32 products and one fp32 add, never contracted.  16-byte accesses when pm and pb are both 16-byte
+ * aligned, element by element otherwise. */
+int vitae_ema_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                    const int* chunks_dev, long n_chunks, long chunk, double m, void* stream);
+/* vitae_lars_multi (optimizer.py:18-43), two launches: entry = (p, g, mu, flags, n, group); flags bit 0 = "p.ndim > 1".
+ *   (1) per chunk of a flagged tensor: sum p^2 and sum (g + wd p)^2 in double -> ws[2 c], ws[2 c + 1];
+ *   (2) per tensor the partials are summed in chunk order (deterministic); q = trust |p| / |dp| when both norms > 0, else 1;
+ *       dp = (g + wd p) q, or dp = g for an unflagged tensor; mu <- momentum mu + dp; p <- p - lr mu.
+ * group_hp_dev: device float[4 * n_groups] sent with the table = lr, weight_decay, momentum, trust_coefficient, n_groups of each.
+ * ws: device double[2 * n_chunks], used between the two launches of one call only.  The chunk list must be in tensor order with
+ * the chunks of a tensor ascending (optim.multi_chunk_list); anything else is VITAE_ERR_INVALID_ARG. */
+#define VITAE_LARS_FLAG_SCALED 1
+int vitae_lars_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                     const int* chunks_dev, long n_chunks, long chunk, const float* group_hp_dev, int n_groups, double* ws,
+                     void* stream);
+/* Both InfoNCE terms of builder.py:63-75,98 and their gradients, three launches: rows normalised as F.normalize (x / max(|x|, 1e-12)),
+ * logits = qn kn^T / T, cross-entropy against the diagonal (row maximum subtracted), mean over N, times 2 T, summed over the pairs
+ * (q1, k2) and (q2, k1).  loss[0] and dq1 / dq2 [N, C] for unit upstream gradient; the clamped norm is a constant; k gets none.
+ * Double arithmetic between the fp32 inputs and the fp32 outputs.  Fixed reduction order, no float atomics: repeats are bit-equal.
+ * ws: vitae_moco_loss_ws_floats(N, C) floats, 16-byte aligned (row losses and row norms, as doubles).
+ * 1 <= N <= VITAE_MOCO_MAX_N, 1 <= C <= VITAE_MOCO_MAX_C, else VITAE_ERR_UNSUPPORTED_SHAPE; T <= 0 or not finite: VITAE_ERR_INVALID_ARG. */
+#define VITAE_MOCO_MAX_N 1024
+#define VITAE_MOCO_MAX_C 4096
+long vitae_moco_loss_ws_floats(int N, int C);
+int vitae_moco_loss(const float* q1, const float* k2, const float* q2, const float* k1, int N, int C, double T, float* loss,
+                    float* dq1, float* dq2, float* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ CSRC = os.path.join(PKG, 'csrc')
 OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(PKG, 'libvitae_hip.so')
 SOURCES = ['gemm.hip', 'gemm_bf16.hip', 'gemm_glds.hip', 'gemm_bt.hip', 'norm.hip', 'attention.hip', 'attention_mfma.hip', 'tokens.hip', 'vit_train.hip', 'classify.hip', 'loss.hip', 'loss_fused.hip',
-           'optim.hip', 'input.hip', 'blur.hip', 'ddp.hip', 'percep.hip']
+           'optim.hip', 'moco.hip', 'input.hip', 'blur.hip', 'ddp.hip', 'percep.hip']
 # -amdgpu-kernarg-preload-count=16: the first 16 dwords of a kernel's scalar / pointer arguments arrive in SGPRs with the dispatch instead
 # of through a cold scalar load at the top of every launch (round 6: the batch-4 step 3.662 -> 3.636 ms, alternating A/B; kernels that take
 # their arguments as ONE by-value struct — the LDS-DMA GEMM family's GArgs — are not covered by the option)
@@ -30,7 +30,10 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=f
 # and with the accumulators in AGPRs (hipcc's default at this register count) each touch was a v_accvgpr_read / _write: 80 of the
 # 170 VALU instructions per 32 x 32 tile of the forward (ISA), 6-12 % of the kernels' time (tools/attn_bench.py).  The GEMM files
 # measured neutral to slightly slower with it (their accumulators are only read once, in the epilogue) and keep the default.
-EXTRA_FLAGS = {'attention_mfma.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
+# moco.hip: no contraction.  The momentum update is specified as two rounded products and one rounded sum, and LARS forms g + wd p in two
+# launches (norm pass, update pass) and must get the same value in both; under -ffp-contract=fast the compiler may fuse either, and that
+# mode ignores `#pragma clang fp contract` (measured: the momentum update one ulp off the statement in ~1 of 4 elements).
+EXTRA_FLAGS = {'attention_mfma.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'moco.hip': ['-ffp-contract=off']}
 
 
 def _hipcc() -> str:

@@ -186,7 +186,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
 // D <= 768 (every model of the reference): each wave owns RPW consecutive rows whose loads are all issued up front;
 // column partials accumulate in registers over the wave's rows and meet the other waves' in LDS in a single round
 // (7.6 us vs 10.8 us for the generic kernel at [440, 768], 8.8 vs 13.2 at [868, 512]).
-template <int RPW>
+// PART (ABI 55): no atomics — the workgroup leaves its three column partials as the record dw[blockIdx.x][3][D] (`dw` is the record
+// workspace then; db and dx_colsum are not touched) for vitae_ln_grad_reduce to add in a fixed order.
+template <int RPW, bool PART = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                  const float* __restrict__ w, const float* __restrict__ mean,
                                                                  const float* __restrict__ rstd, float* __restrict__ dx,
@@ -249,6 +251,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(const float* __
     }
     __syncthreads();
     for (int c = threadIdx.x; c < D; c += 256) {
+        if (PART) {
+            float* rec = dw + (long)blockIdx.x * 3 * D;
+            rec[c] = red[0 * D + c] + red[1 * D + c] + red[2 * D + c] + red[3 * D + c];
+            rec[D + c] = red[4 * D + c] + red[5 * D + c] + red[6 * D + c] + red[7 * D + c];
+            rec[2 * D + c] = red[8 * D + c] + red[9 * D + c] + red[10 * D + c] + red[11 * D + c];
+            continue;
+        }
         atomicAdd(dw + c, red[0 * D + c] + red[1 * D + c] + red[2 * D + c] + red[3 * D + c]);
         atomicAdd(db + c, red[4 * D + c] + red[5 * D + c] + red[6 * D + c] + red[7 * D + c]);
         if (dx_colsum) atomicAdd(dx_colsum + c, red[8 * D + c] + red[9 * D + c] + red[10 * D + c] + red[11 * D + c]);
@@ -562,6 +571,8 @@ __device__ __forceinline__ void bn_sq_acc(double (&q)[4], const f32x4 d) {
     for (int e = 0; e < 4; ++e) q[e] += (double)d[e] * (double)d[e];
 }
 
+// RELU = false (ABI 55, the MoCo v3 heads): plain BatchNorm1d; w == NULL / b == NULL there mean affine=False (weight 1, bias 0)
+template <bool RELU>
 __global__ __launch_bounds__(256) void bn1d_relu_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ b, float* __restrict__ y, __bf16* __restrict__ y16,
                                                             float* __restrict__ save_mean, float* __restrict__ save_rstd,
@@ -613,12 +624,15 @@ __global__ __launch_bounds__(256) void bn1d_relu_fwd_kernel(const float* __restr
     f32x4 rstd;
 #pragma unroll
     for (int e = 0; e < 4; ++e) rstd[e] = (float)(1. / sqrt(q[e] / R + (double)eps));
-    const f32x4 g = *reinterpret_cast<const f32x4*>(w + c), be = *reinterpret_cast<const f32x4*>(b + c);
+    const f32x4 one = {1.f, 1.f, 1.f, 1.f};
+    const f32x4 g = (RELU || w) ? *reinterpret_cast<const f32x4*>(w + c) : one, be = (RELU || b) ? *reinterpret_cast<const f32x4*>(b + c) : z;
     const f32x4 sc = rstd * g;
     for (int r = rg; r < R; r += BN_RG) {
         f32x4 v = ((*reinterpret_cast<const f32x4*>(x + (long)r * D + c) - mean0) - corr) * sc + be;
+        if (RELU) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+        }
         *reinterpret_cast<f32x4*>(y + (long)r * D + c) = v;
         if (y16) {
             bf16x4 h;
@@ -642,6 +656,7 @@ __global__ __launch_bounds__(256) void bn1d_relu_fwd_kernel(const float* __restr
 }
 
 // eval mode (nn.BatchNorm1d with track_running_stats, model.eval()): normalise with the RUNNING statistics
+template <bool RELU>
 __global__ __launch_bounds__(256) void bn1d_relu_eval_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                              const float* __restrict__ b, const float* __restrict__ run_mean,
                                                              const float* __restrict__ run_var, float* __restrict__ y,
@@ -649,11 +664,13 @@ __global__ __launch_bounds__(256) void bn1d_relu_eval_kernel(const float* __rest
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int c = (int)(i % D);
-    const float v = (x[i] - run_mean[c]) * rsqrtf(run_var[c] + eps) * w[c] + b[c];
-    y[i] = v > 0.f ? v : 0.f;
+    const float v = (x[i] - run_mean[c]) * rsqrtf(run_var[c] + eps) * ((RELU || w) ? w[c] : 1.f) + ((RELU || b) ? b[c] : 0.f);
+    y[i] = (!RELU || v > 0.f) ? v : 0.f;
 }
 
 // dy arrives for the ReLU output y; ReLU mask = (y > 0).  dx = w*rstd*(g - mean(g) - xhat*mean(g*xhat)).  Optional bf16 copy of dx.
+// RELU = false: dy is the gradient of the normalised output itself (y is not read and may be NULL); w / dw / db may be NULL (affine=False)
+template <bool RELU>
 __global__ __launch_bounds__(256) void bn1d_relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                             const float* __restrict__ y, const float* __restrict__ w,
                                                             const float* __restrict__ save_mean,
@@ -665,7 +682,8 @@ __global__ __launch_bounds__(256) void bn1d_relu_bwd_kernel(const float* __restr
     const bool ok = c < D;
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     const f32x4 mean = ok ? *reinterpret_cast<const f32x4*>(save_mean + c) : z, rstd = ok ? *reinterpret_cast<const f32x4*>(save_rstd + c) : z;
-    const f32x4 g = ok ? *reinterpret_cast<const f32x4*>(w + c) : z;
+    const f32x4 one = {1.f, 1.f, 1.f, 1.f};
+    const f32x4 g = !ok ? z : (RELU || w) ? *reinterpret_cast<const f32x4*>(w + c) : one;
     f32x4 s1 = z, s2 = z;
     if (ok) {
         int r = rg;
@@ -674,7 +692,7 @@ __global__ __launch_bounds__(256) void bn1d_relu_bwd_kernel(const float* __restr
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const long i = (long)(r + u * BN_RG) * D + c;
-                yv[u] = *reinterpret_cast<const f32x4*>(y + i); dv[u] = *reinterpret_cast<const f32x4*>(dy + i); xv[u] = *reinterpret_cast<const f32x4*>(x + i);
+                yv[u] = RELU ? *reinterpret_cast<const f32x4*>(y + i) : one; dv[u] = *reinterpret_cast<const f32x4*>(dy + i); xv[u] = *reinterpret_cast<const f32x4*>(x + i);
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -686,7 +704,7 @@ __global__ __launch_bounds__(256) void bn1d_relu_bwd_kernel(const float* __restr
         }
         for (; r < R; r += BN_RG) {
             const long i = (long)r * D + c;
-            const f32x4 yv = *reinterpret_cast<const f32x4*>(y + i), dv = *reinterpret_cast<const f32x4*>(dy + i), xv = *reinterpret_cast<const f32x4*>(x + i);
+            const f32x4 yv = RELU ? *reinterpret_cast<const f32x4*>(y + i) : one, dv = *reinterpret_cast<const f32x4*>(dy + i), xv = *reinterpret_cast<const f32x4*>(x + i);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float d = yv[e] > 0.f ? dv[e] : 0.f;
@@ -697,14 +715,14 @@ __global__ __launch_bounds__(256) void bn1d_relu_bwd_kernel(const float* __restr
     s1 = bn_col_reduce4(s1, red, cg, rg);
     s2 = bn_col_reduce4(s2, red, cg, rg);
     if (!ok) return;
-    if (rg == 0) {
+    if (rg == 0 && (RELU || dw)) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) { atomicAdd(dw + c + e, s2[e]); atomicAdd(db + c + e, s1[e]); }
     }
     const f32x4 m1 = s1 / (float)R, m2 = s2 / (float)R;
     for (int r = rg; r < R; r += BN_RG) {
         const long i = (long)r * D + c;
-        const f32x4 yv = *reinterpret_cast<const f32x4*>(y + i), dv = *reinterpret_cast<const f32x4*>(dy + i), xv = *reinterpret_cast<const f32x4*>(x + i);
+        const f32x4 yv = RELU ? *reinterpret_cast<const f32x4*>(y + i) : one, dv = *reinterpret_cast<const f32x4*>(dy + i), xv = *reinterpret_cast<const f32x4*>(x + i);
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -995,6 +1013,19 @@ extern "C" int vitae_layernorm_bwd_part(const float* dy, const float* x, const f
     return vitae_launch_status();
 }
 
+// The record form for every other D <= 768 (D % 4 == 0: vitae_ln_grad_reduce moves float4 groups): the generic rows kernel, one record
+// per workgroup of VITAE_LN_PART_ANY_ROWS rows.
+extern "C" int vitae_layernorm_bwd_part_any(const float* dy, const float* x, const float* w, const float* mean, const float* rstd,
+                                            float* dx, float* part, void* dx_bf16, int M, int D, int dx_accumulate, void* stream) {
+    if (!dy || !x || !w || !mean || !rstd || !dx || !part || M <= 0 || D <= 0) return VITAE_ERR_INVALID_ARG;
+    if (D > 768 || (D & 3) || ((uintptr_t)part & 15)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    static_assert(VITAE_LN_PART_ANY_ROWS == 8, "layernorm_bwd_rows_kernel<2>: 4 waves x 2 rows per workgroup");
+    hipLaunchKernelGGL((layernorm_bwd_rows_kernel<2, true>), dim3(cdiv(M, VITAE_LN_PART_ANY_ROWS)), dim3(256), (size_t)12 * D * sizeof(float),
+                       (hipStream_t)stream, dy, x, w, mean, rstd, dx, part, (float*)nullptr, reinterpret_cast<__bf16*>(dx_bf16),
+                       (float*)nullptr, M, D, dx_accumulate);
+    return vitae_launch_status();
+}
+
 // n instances; the arrays live on the HOST (copied into the launch's arguments)
 extern "C" int vitae_ln_grad_reduce(int n, const float* const* part, float* const* dw, float* const* db, float* const* dx_colsum,
                                     const int* records, const int* D, void* stream) {
@@ -1019,6 +1050,38 @@ extern "C" int vitae_ln_grad_reduce(int n, const float* const* part, float* cons
     return vitae_launch_status();
 }
 
+// The same sum without atomics (ABI 55): row-slab partials, then their sum in slab order.  Bitwise reproducible.
+namespace {
+constexpr int COLSUM_ORDERED_ROWS = 32;
+__global__ __launch_bounds__(256) void colsum_part_kernel(const float* __restrict__ dy, long ld, float* __restrict__ part, int M, int N) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const int r0 = blockIdx.y * COLSUM_ORDERED_ROWS, r1 = min(M, r0 + COLSUM_ORDERED_ROWS);
+    float s = 0.f;
+    for (int m = r0; m < r1; ++m) s += dy[(long)m * ld + n];
+    part[(long)blockIdx.y * N + n] = s;
+}
+__global__ __launch_bounds__(256) void colsum_slabs_kernel(const float* __restrict__ part, float* __restrict__ out, int slabs, int N) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    float s = 0.f;
+    for (int b = 0; b < slabs; ++b) s += part[(long)b * N + n];
+    out[n] += s;
+}
+}  // namespace
+
+extern "C" long vitae_colsum_ordered_ws_floats(int M, int N) {
+    return M > 0 && N > 0 ? (long)cdiv(M, COLSUM_ORDERED_ROWS) * N : 0;
+}
+
+extern "C" int vitae_colsum_ordered(const float* dy, long ld, float* out, float* ws, int M, int N, void* stream) {
+    if (!dy || !out || !ws || M <= 0 || N <= 0 || ld < N) return VITAE_ERR_INVALID_ARG;
+    const int slabs = cdiv(M, COLSUM_ORDERED_ROWS);
+    hipLaunchKernelGGL(colsum_part_kernel, dim3(cdiv(N, 256), slabs), dim3(256), 0, (hipStream_t)stream, dy, ld, ws, M, N);
+    hipLaunchKernelGGL(colsum_slabs_kernel, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, ws, out, slabs, N);
+    return vitae_launch_status();
+}
+
 extern "C" int vitae_colsum_accum(const float* dy, long ld, float* out, int M, int N, void* stream) {
     if (!dy || !out || M <= 0 || N <= 0) return VITAE_ERR_INVALID_ARG;
     const int rpb = 32;
@@ -1040,7 +1103,7 @@ extern "C" int vitae_bn1d_relu_fwd(const float* x, const float* w, const float* 
     if (!x || !w || !b || !y || !save_mean || !save_rstd || R <= 0 || D <= 0) return VITAE_ERR_INVALID_ARG;
     if (!bn_vec_ok(D, {x, w, b, y, save_mean, save_rstd}) || ((uintptr_t)y_bf16 & 7)) return VITAE_ERR_UNSUPPORTED_SHAPE;
     if (!running_mean) num_batches_tracked = nullptr;      // no running statistics: the step is not counted either
-    hipLaunchKernelGGL(bn1d_relu_fwd_kernel, dim3(cdiv(D, BN_COLS)), dim3(256), 0, (hipStream_t)stream, x, w, b, y,
+    hipLaunchKernelGGL(bn1d_relu_fwd_kernel<true>, dim3(cdiv(D, BN_COLS)), dim3(256), 0, (hipStream_t)stream, x, w, b, y,
                        reinterpret_cast<__bf16*>(y_bf16), save_mean, save_rstd, running_mean, running_var, num_batches_tracked, R, D, eps, momentum);
     return vitae_launch_status();
 }
@@ -1049,7 +1112,7 @@ extern "C" int vitae_bn1d_relu_eval(const float* x, const float* w, const float*
                                     const float* running_var, float* y, int R, int D, float eps, void* stream) {
     if (!x || !w || !b || !running_mean || !running_var || !y || R <= 0 || D <= 0) return VITAE_ERR_INVALID_ARG;
     const long n = (long)R * D;
-    hipLaunchKernelGGL(bn1d_relu_eval_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x, w, b, running_mean,
+    hipLaunchKernelGGL(bn1d_relu_eval_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x, w, b, running_mean,
                        running_var, y, n, D, eps);
     return vitae_launch_status();
 }
@@ -1060,8 +1123,40 @@ extern "C" int vitae_bn1d_relu_bwd(const float* dy, const float* x, const float*
     if (!dy || !x || !y || !w || !save_mean || !save_rstd || !dx || !dw || !db || R <= 0 || D <= 0)
         return VITAE_ERR_INVALID_ARG;
     if (!bn_vec_ok(D, {dy, x, y, w, save_mean, save_rstd, dx}) || ((uintptr_t)dx_bf16 & 7)) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    hipLaunchKernelGGL(bn1d_relu_bwd_kernel, dim3(cdiv(D, BN_COLS)), dim3(256), 0, (hipStream_t)stream, dy, x, y, w,
+    hipLaunchKernelGGL(bn1d_relu_bwd_kernel<true>, dim3(cdiv(D, BN_COLS)), dim3(256), 0, (hipStream_t)stream, dy, x, y, w,
                        save_mean, save_rstd, dx, reinterpret_cast<__bf16*>(dx_bf16), dw, db, R, D);
+    return vitae_launch_status();
+}
+
+// ---- plain BatchNorm1d (ABI 55: the projector / predictor of other_baselines/mocov3): the kernels above without the ReLU
+extern "C" int vitae_bn1d_fwd(const float* x, const float* w, const float* b, float* y, void* y_bf16, float* save_mean,
+                              float* save_rstd, float* running_mean, float* running_var, long long* num_batches_tracked, int R, int D,
+                              float eps, float momentum, void* stream) {
+    if (!x || !y || !save_mean || !save_rstd || R <= 0 || D <= 0 || (!w != !b)) return VITAE_ERR_INVALID_ARG;
+    if (!bn_vec_ok(D, {x, w, b, y, save_mean, save_rstd}) || ((uintptr_t)y_bf16 & 7)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (!running_mean) num_batches_tracked = nullptr;
+    else if (!running_var) return VITAE_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(bn1d_relu_fwd_kernel<false>, dim3(cdiv(D, BN_COLS)), dim3(256), 0, (hipStream_t)stream, x, w, b, y,
+                       reinterpret_cast<__bf16*>(y_bf16), save_mean, save_rstd, running_mean, running_var, num_batches_tracked, R, D, eps, momentum);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_bn1d_eval(const float* x, const float* w, const float* b, const float* running_mean, const float* running_var,
+                               float* y, int R, int D, float eps, void* stream) {
+    if (!x || !running_mean || !running_var || !y || R <= 0 || D <= 0 || (!w != !b)) return VITAE_ERR_INVALID_ARG;
+    if (!bn_vec_ok(D, {x, w, b, running_mean, running_var, y})) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    const long n = (long)R * D;
+    hipLaunchKernelGGL(bn1d_relu_eval_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x, w, b, running_mean,
+                       running_var, y, n, D, eps);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_bn1d_bwd(const float* dy, const float* x, const float* w, const float* save_mean, const float* save_rstd,
+                              float* dx, void* dx_bf16, float* dw, float* db, int R, int D, void* stream) {
+    if (!dy || !x || !save_mean || !save_rstd || !dx || R <= 0 || D <= 0 || (!dw != !db) || (dw && !w)) return VITAE_ERR_INVALID_ARG;
+    if (!bn_vec_ok(D, {dy, x, w, save_mean, save_rstd, dx}) || ((uintptr_t)dx_bf16 & 7)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    hipLaunchKernelGGL(bn1d_relu_bwd_kernel<false>, dim3(cdiv(D, BN_COLS)), dim3(256), 0, (hipStream_t)stream, dy, x,
+                       (const float*)nullptr, w, save_mean, save_rstd, dx, reinterpret_cast<__bf16*>(dx_bf16), dw, db, R, D);
     return vitae_launch_status();
 }
 

@@ -28,6 +28,14 @@ _ALIASES = {
     'utils.mixup': 'vit_ae_plus_plus_amd.utils.mixup',
     'post_training_utils': 'vit_ae_plus_plus_amd.post_training_utils',
     'post_training_utils.fine_tune_epoch': 'vit_ae_plus_plus_amd.post_training_utils.fine_tune_epoch',
+    # the MoCo v3 baseline (other_baselines/mocov3/main_3d_moco_k_fold.py: `import other_baselines.mocov3.moco.builder` / `.optimizer`)
+    'other_baselines': 'vit_ae_plus_plus_amd.other_baselines',
+    'other_baselines.mocov3': 'vit_ae_plus_plus_amd.other_baselines.mocov3',
+    'other_baselines.mocov3.moco': 'vit_ae_plus_plus_amd.other_baselines.mocov3.moco',
+    'other_baselines.mocov3.moco.builder': 'vit_ae_plus_plus_amd.other_baselines.mocov3.moco.builder',
+    'other_baselines.mocov3.moco.optimizer': 'vit_ae_plus_plus_amd.other_baselines.mocov3.moco.optimizer',
+    # (the baseline's own copy of the encoder is model/vit.py without the contrastive class)
+    'other_baselines.mocov3.moco.vit_3d': 'vit_ae_plus_plus_amd.model.vit',
 }
 
 

@@ -18,6 +18,7 @@ route) share the frame ``_Trainer``: the same embedding, block forward and pooli
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, Tuple
 
 import torch
@@ -347,11 +348,34 @@ class _Trainer(HipEncoder):
                                     + sum(t.numel() * t.element_size() for t in (kept['patches'], pool, mean, rstd) if t is not None))
         return feat, kept
 
+    def _colsum(self, dy_ptr, ld, out, M, N):
+        """out[n] += sum_m dy[m, n] (a bias gradient); in a fixed order when the module asks for it (``ordered_norm_grads``, see _ln_bwd)."""
+        if getattr(self.m, 'ordered_norm_grads', False):
+            ws = self._f(int(lib.vitae_colsum_ordered_ws_floats(M, N)))
+            lib.vitae_colsum_ordered(dy_ptr, ld, _ptr(out), _ptr(ws), M, N, self.stream)
+        else:
+            lib.vitae_colsum_accum(dy_ptr, ld, _ptr(out), M, N, self.stream)
+
     def _ln_bwd(self, grads, needs, dy, x, pre, mean, rstd, dx, M, D, dx_accumulate, dx16=None, dx_colsum=None):
         """LayerNorm backward: dx (+)= ..., optionally its bf16 copy ``dx16`` and its column sums added to ``dx_colsum``."""
         dw, db = self._z(D), self._z(D)             # the launcher adds its column partials
-        lib.vitae_layernorm_bwd(_ptr(dy), _ptr(x), _ptr(self._param(pre + 'weight')), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dw),
-                                _ptr(db), _ptr(dx16), _ptr(dx_colsum), M, D, dx_accumulate, self.stream)
+        if getattr(self.m, 'ordered_norm_grads', False):
+            if D % 4 or (D > 768 and D != 1024):        # (no quiet return to the atomic form: the flag promises reproducible sums)
+                raise VitaeError(f'ordered_norm_grads: the atomic-free LayerNorm backward serves D % 4 == 0 up to 768, and 1024 (got {D})')
+            # no atomics (set by other_baselines.mocov3.moco.builder.MoCo on its base encoder): every workgroup leaves its partials
+            # as a record and one reduce launch adds the records in a fixed order, so these gradients reproduce bit for bit
+            vec = D in (256, 512, 768, 1024)
+            G = lib.vitae_layernorm_bwd_part_records(M) if vec else -(-M // _C['VITAE_LN_PART_ANY_ROWS'])
+            part = self._f(G * 3 * D)
+            (lib.vitae_layernorm_bwd_part if vec else lib.vitae_layernorm_bwd_part_any)(
+                _ptr(dy), _ptr(x), _ptr(self._param(pre + 'weight')), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(part), _ptr(dx16), M, D,
+                dx_accumulate, self.stream)
+            one = lambda v, t=ctypes.c_void_p: (t * 1)(v)
+            lib.vitae_ln_grad_reduce(1, one(part.data_ptr()), one(dw.data_ptr()), one(db.data_ptr()), one(_ptr(dx_colsum)),
+                                     one(G, ctypes.c_int), one(D, ctypes.c_int), self.stream)
+        else:
+            lib.vitae_layernorm_bwd(_ptr(dy), _ptr(x), _ptr(self._param(pre + 'weight')), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dw),
+                                    _ptr(db), _ptr(dx16), _ptr(dx_colsum), M, D, dx_accumulate, self.stream)
         if needs.get(pre + 'weight'):
             grads[pre + 'weight'] = dw
         if needs.get(pre + 'bias'):
@@ -425,7 +449,7 @@ class HipEncoderTrainer(_Trainer):
             lib.vitae_linear_bwd_weight(self.prec, _ptr(dy), _ptr(x), _ptr(dw), M, N, K, 0, self._split_bwd(N, K, M), ws, self.stream)
         if needs.get(bname):
             db = grads[bname] = self._z(N)          # the column-sum launcher adds
-            lib.vitae_colsum_accum(_ptr(dy), N, _ptr(db), M, N, self.stream)
+            self._colsum(_ptr(dy), N, db, M, N)
         if dx is not None:
             lib.vitae_linear_bwd_input(self.prec, _ptr(dy), _ptr(self._param(wname)), _ptr(dx), M, N, K, epi, _ptr(aux), 0,
                                        self._split_bwd(M, K, N), ws, self.stream)
@@ -607,7 +631,7 @@ class HipEncoderTrainer16(_Trainer):
             if want_b:
                 # colsum(dtok) = sum over the patch rows of dpos (dpos[n] = sum_b dx[b, n]): L rows instead of B L
                 db = grads['patch_embed.proj.bias'] = self._z(D)
-                lib.vitae_colsum_accum(dpos.data_ptr() + 4 * D, D, _ptr(db), L, D, st)
+                self._colsum(dpos.data_ptr() + 4 * D, D, db, L, D)
             if want_w:
                 # dW[D, P] = dtok16^T @ patches16 (both row-contiguous bf16, reduced over the padded token count)
                 dw = grads['patch_embed.proj.weight'] = torch.empty_like(self._param('patch_embed.proj.weight'))
