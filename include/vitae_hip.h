@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define VITAE_ABI_VERSION 55
+#define VITAE_ABI_VERSION 56
 
 /* matrix-core arithmetic of the dense contractions */
 #define VITAE_PREC_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32 (the reference's precision, autocast off at utils/train_one_epoch.py:50) */
@@ -658,6 +658,65 @@ int vitae_lars_multi(const long long* table_host, const long long* table_dev, lo
 long vitae_moco_loss_ws_floats(int N, int C);
 int vitae_moco_loss(const float* q1, const float* k2, const float* q2, const float* k1, int N, int C, double T, float* loss,
                     float* dq1, float* dq2, float* ws, void* stream);
+
+/* ---- 3-D ResNet baseline (ABI 56; k_fold_training_scripts/resnet_3d.py) ---------------------------------------------------
+ * Inside the network activations are channels-last, [N, D, H, W, C] = rows x channels.  A convolution is a gather-GEMM over
+ * K = taps * Cin on v_mfma_f32_32x32x16_bf16 (bf16 operands, fp32 accumulate); no im2col buffer exists.
+ * Geometry of every conv call: input [N, D, H, W, Cin], kernel (kd, kh, kw) in 1..7, stride (sd, sh, sw) in {1, 2}, padding
+ * (pd, ph, pw) in [0, k), output extent Do = (D + 2 pd - kd) / sd + 1 (likewise Ho, Wo), M = N Do Ho Wo rows.
+ * Cout % 4 == 0; Cin == 1..3 (gathered element by element: the stem) or Cin % 4 == 0.  Operands 16-byte aligned.
+ * A source voxel outside the volume contributes zero; every gather is predicated, so no address outside an operand is formed.
+ * Offsets are 64-bit; a row count or a K that does not fit an int is VITAE_ERR_UNSUPPORTED_SHAPE.  Fixed summation order
+ * everywhere, no float atomics: repeats are bit-equal.  Every launcher refuses before its first launch and then writes nothing.
+ *
+ * Packed weight: bf16 [rows][Kpad], Kpad = K rounded up to VITAE_CONV3D_K_STEP, the tail of each row zero.
+ *   transposed = 0 (forward operand):        rows = Cout, k = tap * Cin + ci;
+ *   transposed = 1 (input-gradient operand): rows = Cin,  k = tap * Cout + co.        tap = (kd_i * kh + kh_i) * kw + kw_i.
+ * vitae_conv3d_pack_weight reads torch's [Cout, Cin, kd, kh, kw] fp32; re-run it after each optimiser step. */
+#define VITAE_CONV3D_K_STEP 16
+#define VITAE_CONV3D_WGRAD_CHUNK 4096 /* rows of M per partial of vitae_conv3d_bwd_weight */
+long vitae_conv3d_packed_elems(int Cout, int Cin, int kd, int kh, int kw, int transposed);
+int vitae_conv3d_pack_weight(const float* w, void* w16, int Cout, int Cin, int kd, int kh, int kw, int transposed, void* stream);
+/* [N, C, D, H, W] fp32 -> [N, D, H, W, C] bf16 (the network input) */
+int vitae_to_channels_last_bf16(const float* x, void* x16, int N, int C, int D, int H, int W, void* stream);
+/* y[m, co] = sum_{tap, ci} x16[src(m, tap), ci] w16[co, tap, ci]; y fp32 and / or y_bf16 (at least one) */
+int vitae_conv3d_fwd(const void* x16, const void* w16, float* y, void* y_bf16, int N, int D, int H, int W, int Cin, int Cout,
+                     int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream);
+/* dx[v, ci] = sum over the taps whose output position exists (the stride divides the offset) and co of dy16[dst(v, tap), co] w[co, tap, ci]:
+ * a gather over dy16 [N, Do, Ho, Wo, Cout] with the transposed packed weight.  dx fp32 and / or dx_bf16.  accumulate != 0 (needs dx):
+ * the sum is added to what dx holds — the residual branch's gradient — and dx_bf16 is the copy of that total. */
+int vitae_conv3d_bwd_input(const void* dy16, const void* w16t, float* dx, void* dx_bf16, int accumulate, int N, int D, int H, int W, int Cin, int Cout,
+                           int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream);
+/* dW[co, ci, tap] (torch layout, fp32) = sum_m dy16[m, co] x16[src(m, tap), ci]; accumulate != 0: added to dW, else overwritten.
+ * Two launches: a partial per chunk of VITAE_CONV3D_WGRAD_CHUNK rows into ws [chunks][Cout][taps * Cin], then their sum in chunk order.
+ * ws_floats (the size the caller allocated) below vitae_conv3d_wgrad_ws_floats(...) is VITAE_ERR_INVALID_ARG. */
+long vitae_conv3d_wgrad_ws_floats(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw,
+                                  int pd, int ph, int pw);
+int vitae_conv3d_bwd_weight(const void* dy16, const void* x16, float* dw, float* ws, long ws_floats, int accumulate, int N, int D, int H,
+                            int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream);
+/* MaxPool3d(kernel 3, stride 2, padding 1), channels-last: x fp32 [N, D, H, W, C] -> y / y_bf16 [N, Do, Ho, Wo, C] (at least one) and
+ * idx: one uint8 per output, the tap (kd_i * 3 + kh_i) * 3 + kw_i of the maximum.  Padding is -inf; the scan is torch's (d, h, w
+ * ascending; a value replaces the maximum when it is greater or NaN).  bwd: each input voxel visits the <= 8 windows that contain
+ * it and adds dy where the saved index points at it (a gather, no atomics); dx fp32 and / or dx_bf16. */
+int vitae_maxpool3d_fwd(const float* x, float* y, void* y_bf16, void* idx, int N, int D, int H, int W, int C, void* stream);
+int vitae_maxpool3d_bwd(const float* dy, const void* idx, float* dx, void* dx_bf16, int N, int D, int H, int W, int C, void* stream);
+/* Global average pool: x [N, S, C] -> y [N, C] (+ bf16 copy), summed in row order; bwd: dx[n, s, c] = dy[n, c] / S (fp32 and / or bf16) */
+int vitae_rows_mean_fwd(const float* x, float* y, void* y_bf16, int N, int S, int C, void* stream);
+int vitae_rows_mean_bwd(const float* dy, float* dx, void* dx_bf16, int N, int S, int C, void* stream);
+/* The BasicBlock tail y = [relu](bn(x) [+ res]) on channels-last rows (R = N D H W rows, C columns), rows split over workgroups on the
+ * machinery of vitae_bn1d_relu_*_split (two launches, Chan's merge, deterministic; ws of vitae_bn1d_split_ws_floats(R, C) floats).
+ * res == NULL: no residual; relu == 0 and res == NULL is plain BatchNorm3d at many rows (the downsample branch).  C % 4 == 0,
+ * 16-byte aligned operands, double sums, two-float mean, unbiased running variance, num_batches_tracked as the forms above.
+ * bwd: dy is the gradient of y; the ReLU mask is y > 0 (y may be NULL when relu == 0); dres (optional: the block
+ * had a residual) receives the masked gradient; dw / db are accumulated into. */
+int vitae_bn_tail_fwd_split(const float* x, const float* res, const float* w, const float* b, float* y, void* y_bf16, float* save_mean,
+                            float* save_rstd, float* running_mean, float* running_var, long long* num_batches_tracked, int R, int C,
+                            float eps, float momentum, int relu, float* ws, void* stream);
+int vitae_bn_tail_eval(const float* x, const float* res, const float* w, const float* b, const float* running_mean,
+                       const float* running_var, float* y, void* y_bf16, int R, int C, float eps, int relu, void* stream);
+int vitae_bn_tail_bwd_split(const float* dy, const float* x, const float* y, const float* w, const float* save_mean,
+                            const float* save_rstd, float* dx, void* dx_bf16, float* dres, float* dw_accum, float* db_accum,
+                            int R, int C, int relu, float* ws, void* stream);
 
 #ifdef __cplusplus
 }

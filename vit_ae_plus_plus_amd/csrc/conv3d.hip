@@ -1,0 +1,492 @@
+// 3-D ResNet baseline (k_fold_training_scripts/resnet_3d.py): Conv3d forward / input gradient / weight gradient as gather-GEMMs on
+// v_mfma_f32_32x32x16_bf16, MaxPool3d(3, 2, 1), the global average pool, and the packing of their operands.
+//
+// Activations are channels-last [N, D, H, W, C] = rows x channels, so a convolution is C[M, Cout] = A[M, K] B[Cout, K]^T with
+// K = taps * Cin and A never materialised: every lane gathers the 8 k-values of its MFMA fragment straight from the activation
+// (one 16-byte load when Cin % 8 == 0, two 8-byte loads when Cin % 4 == 0, element by element otherwise: the 1-channel stem).
+// The input gradient is the SAME kernel with the coordinate rule turned round (source = dy16, a tap contributes when the stride
+// divides the offset) and the transposed packed weight.  The weight gradient reduces over the rows M in chunks of
+// VITAE_CONV3D_WGRAD_CHUNK: a partial per chunk into the caller's workspace, summed in chunk order by a second launch.
+//
+// MFMA operand maps (32x32x16 bf16): lane l, r = l & 31, h = l >> 5 holds A[row r][k = 8 h + j] and B[k = 8 h + j][col r], j = 0..7;
+// the result has col = l & 31 and row = (reg & 3) + 8 (reg >> 2) + 4 h.
+//
+// Safety: a gather is issued only under its predicate (row in range, k < K, source voxel inside the volume), so no address outside
+// an operand is formed; offsets are 64-bit.  No LDS beyond a 343-entry tap table / a 64-row coordinate table.
+#include "common.hpp"
+#include "vitae_hip.h"
+
+#include <limits.h>
+#include <initializer_list>
+
+namespace {
+
+constexpr int KSTEP = VITAE_CONV3D_K_STEP;
+constexpr int MAX_TAPS = 7 * 7 * 7;
+constexpr int WCHUNK = VITAE_CONV3D_WGRAD_CHUNK;
+// Two-level accumulation: the MFMA chain runs FLUSH k-steps (128 k-values) in fp32 and is then added to a double total.  One fp32
+// chain over the stem's 1372 steps (all products of one sign) was 18 ulp off in the worst element, 4.6 x torch's blocked fp32 sum.
+constexpr int FLUSH = 8;
+
+__device__ __forceinline__ void flush_acc(f32x16& acc, double (&tot)[16]) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { tot[i] += (double)acc[i]; acc[i] = 0.f; }
+}
+
+struct ConvGeo {
+    int N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw;
+    int Do, Ho, Wo, taps;
+    long M, V;          // output rows N Do Ho Wo, input voxels N D H W
+    long K;             // taps * Cin
+};
+
+// VITAE_OK or the refusal; fills g
+int conv_geo(ConvGeo& g, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw) {
+    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return VITAE_ERR_INVALID_ARG;
+    if (kd < 1 || kh < 1 || kw < 1 || kd > 7 || kh > 7 || kw > 7) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (sd < 1 || sh < 1 || sw < 1 || sd > 2 || sh > 2 || sw > 2) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (pd < 0 || ph < 0 || pw < 0 || pd >= kd || ph >= kh || pw >= kw) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (Cout & 3) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (D + 2 * pd < kd || H + 2 * ph < kh || W + 2 * pw < kw) return VITAE_ERR_UNSUPPORTED_SHAPE;      // an output extent <= 0
+    g = ConvGeo{N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw};
+    g.Do = (D + 2 * pd - kd) / sd + 1; g.Ho = (H + 2 * ph - kh) / sh + 1; g.Wo = (W + 2 * pw - kw) / sw + 1;
+    g.taps = kd * kh * kw;
+    g.M = (long)N * g.Do * g.Ho * g.Wo;
+    g.V = (long)N * D * H * W;
+    g.K = (long)g.taps * Cin;
+    const long lim = (long)INT_MAX - 256;
+    if (g.M > lim || g.V > lim || g.K > lim || (long)g.taps * Cout > lim) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    return VITAE_OK;
+}
+
+inline long kpad(long K) { return (K + KSTEP - 1) / KSTEP * KSTEP; }
+inline int shift_of(int c) { return (c & (c - 1)) == 0 ? __builtin_ctz(c) : -1; }
+inline bool aligned16(std::initializer_list<const void*> ptrs) {
+    for (const void* q : ptrs) if ((uintptr_t)q & 15) return false;
+    return true;
+}
+
+// ------------------------------------------------------------------ packing
+__global__ __launch_bounds__(256) void conv3d_pack_kernel(const float* __restrict__ w, __bf16* __restrict__ out, int Cout, int Cin, int taps,
+                                                          int Kp, int transposed, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int row = (int)(i / Kp), k = (int)(i % Kp);
+    const int inner = transposed ? Cout : Cin;          // k = tap * inner + c
+    float v = 0.f;
+    if (k < taps * inner) {
+        const int tap = k / inner, c = k % inner;
+        const int co = transposed ? c : row, ci = transposed ? row : c;
+        v = w[((long)co * Cin + ci) * taps + tap];
+    }
+    out[i] = (__bf16)v;
+}
+
+__global__ __launch_bounds__(256) void channels_last_bf16_kernel(const float* __restrict__ x, __bf16* __restrict__ out, int C, long S, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;      // output index: (n S + s) C + c
+    if (i >= total) return;
+    const int c = (int)(i % C);
+    const long ns = i / C, n = ns / S, s = ns % S;
+    out[i] = (__bf16)x[(n * C + c) * S + s];
+}
+
+// ------------------------------------------------------------------ forward / input gradient: one gather-GEMM
+struct GatherArgs {
+    const __bf16* src; const __bf16* wpk; float* out; __bf16* out16;
+    int Ds, Hs, Ws, Cs;         // source volume of one sample, its channels
+    int Dr, Hr, Wr;             // row space of one sample
+    int M, Nout;                // rows, output columns
+    int kd, kh, kw, sd, sh, sw, pd, ph, pw;
+    int K, Kp, cs_shift;        // K = taps * Cs; Kp = K padded to the k step; log2(Cs) or -1
+    int accum;                  // != 0: the result is added to what `out` holds
+};
+
+// One axis of the coordinate rule.  Forward: source = row * stride - pad + tap.  Input gradient: t = voxel + pad - tap must be a
+// non-negative multiple of the stride (1 or 2) and t / stride an existing output position.
+template <bool BWD>
+__device__ __forceinline__ bool conv_axis(int base, int tap, int stride, int extent, int& c) {
+    if (!BWD) { c = base + tap; return c >= 0 && c < extent; }
+    const int t = base - tap;
+    c = t >> (stride - 1);
+    return t >= 0 && (t & (stride - 1)) == 0 && c < extent;
+}
+
+template <int G, bool BWD>
+__global__ __launch_bounds__(256) void conv3d_gather_kernel(const GatherArgs a) {
+    __shared__ int tab[MAX_TAPS];                                    // tap -> kd_i << 16 | kh_i << 8 | kw_i
+    const int taps = a.kd * a.kh * a.kw;
+    for (int t = threadIdx.x; t < taps; t += 256) {
+        const int r = t / a.kw;
+        tab[t] = ((r / a.kh) << 16) | ((r % a.kh) << 8) | (t % a.kw);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
+    const int row0 = blockIdx.x * 128 + wave * 32;
+    const int m = row0 + l31;                                        // the row of this lane's A fragment
+    const bool mok = m < a.M;
+    int n = 0, bd = 0, bh = 0, bw = 0;
+    if (mok) {
+        int r = m;
+        const int wr = r % a.Wr; r /= a.Wr;
+        const int hr = r % a.Hr; r /= a.Hr;
+        const int dr = r % a.Dr; n = r / a.Dr;
+        bd = BWD ? dr + a.pd : dr * a.sd - a.pd;
+        bh = BWD ? hr + a.ph : hr * a.sh - a.ph;
+        bw = BWD ? wr + a.pw : wr * a.sw - a.pw;
+    }
+    const int co = blockIdx.y * 32 + l31;                            // the column of this lane's B fragment
+    const bool cok = co < a.Nout;
+    const __bf16* wrow = a.wpk + (long)(cok ? co : 0) * a.Kp + 8 * hi;
+    const long nbase = (long)n * a.Ds;
+
+    f32x16 acc;
+    double tot[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc[i] = 0.f; tot[i] = 0.; }
+    int chain = 0;
+    for (int k0 = 0; k0 < a.Kp; k0 += KSTEP) {
+        bf16x8 av, bv;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { av[j] = (__bf16)0.f; bv[j] = (__bf16)0.f; }
+        if (cok) bv = *reinterpret_cast<const bf16x8*>(wrow + k0);
+#pragma unroll
+        for (int g = 0; g < 8 / G; ++g) {
+            const int k = k0 + 8 * hi + g * G;
+            if (!mok || k >= a.K) continue;                          // the zero tail of K: predicated, not multiplied by zero weights
+            const int tap = a.cs_shift >= 0 ? k >> a.cs_shift : k / a.Cs;
+            const int ci = k - tap * a.Cs;
+            const int t = tab[tap];
+            int d, h, w;
+            const bool ok = conv_axis<BWD>(bd, t >> 16, a.sd, a.Ds, d) & conv_axis<BWD>(bh, (t >> 8) & 255, a.sh, a.Hs, h) &
+                            conv_axis<BWD>(bw, t & 255, a.sw, a.Ws, w);
+            if (!ok) continue;
+            const __bf16* p = a.src + (((nbase + d) * a.Hs + h) * a.Ws + w) * a.Cs + ci;
+            if (G == 8) av = *reinterpret_cast<const bf16x8*>(p);
+            else if (G == 4) {
+                const bf16x4 q = *reinterpret_cast<const bf16x4*>(p);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) av[4 * g + e] = q[e];
+            } else av[g] = *p;
+        }
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
+        if (++chain == FLUSH) { flush_acc(acc, tot); chain = 0; }
+    }
+    flush_acc(acc, tot);
+    if (!cok) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int mm = row0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        if (mm >= a.M) continue;
+        const long o = (long)mm * a.Nout + co;
+        float v = (float)tot[r];
+        if (a.accum) v += a.out[o];
+        if (a.out) a.out[o] = v;
+        if (a.out16) a.out16[o] = (__bf16)v;
+    }
+}
+
+template <bool BWD>
+void launch_gather(const GatherArgs& a, hipStream_t st) {
+    const dim3 grid(cdiv(a.M, 128), cdiv(a.Nout, 32));
+    if (a.Cs % 8 == 0) hipLaunchKernelGGL((conv3d_gather_kernel<8, BWD>), grid, dim3(256), 0, st, a);
+    else if (a.Cs % 4 == 0) hipLaunchKernelGGL((conv3d_gather_kernel<4, BWD>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv3d_gather_kernel<1, BWD>), grid, dim3(256), 0, st, a);
+}
+
+// ------------------------------------------------------------------ weight gradient
+// Workgroup = (128 k-columns: 32 per wave) x (32 output channels) x (one chunk of rows).  MFMA: A[row = co][k = m] = dy16[m, co],
+// B[k = m][col = kcol] = x16[src(m, tap(kcol)), ci(kcol)].  The 8 rows of a lane's fragments are the same for the 32 lanes of a
+// half wave; their decoded coordinates come from a 64-row table in LDS that the first wave refills every 64 rows.
+__global__ __launch_bounds__(256) void conv3d_wgrad_part_kernel(const __bf16* __restrict__ dy16, const __bf16* __restrict__ x16,
+                                                                float* __restrict__ ws, const ConvGeo g) {
+    __shared__ int4 rowtab[64];                                       // n (or -1 past the chunk), od sd - pd, oh sh - ph, ow sw - pw
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
+    const int K = (int)g.K, M = (int)g.M;
+    const int kcol = blockIdx.x * 128 + wave * 32 + l31;
+    const bool kok = kcol < K;
+    const int tap = kok ? kcol / g.Cin : 0, ci = kok ? kcol % g.Cin : 0;
+    const int tkw = tap % g.kw, tkh = (tap / g.kw) % g.kh, tkd = tap / (g.kw * g.kh);
+    const int co = blockIdx.y * 32 + l31;
+    const bool cok = co < g.Cout;
+    const int m_begin = blockIdx.z * WCHUNK, m_end = min(M, m_begin + WCHUNK);
+
+    f32x16 acc;
+    double tot[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc[i] = 0.f; tot[i] = 0.; }
+    for (int mb = m_begin; mb < m_end; mb += 64) {
+        if (((mb - m_begin) & (FLUSH * KSTEP - 1)) == 0) flush_acc(acc, tot);
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const int m = mb + threadIdx.x;
+            int4 e = make_int4(-1, 0, 0, 0);
+            if (m < m_end) {
+                int r = m;
+                const int ow = r % g.Wo; r /= g.Wo;
+                const int oh = r % g.Ho; r /= g.Ho;
+                const int od = r % g.Do;
+                e = make_int4(r / g.Do, od * g.sd - g.pd, oh * g.sh - g.ph, ow * g.sw - g.pw);
+            }
+            rowtab[threadIdx.x] = e;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            if (mb + ks * KSTEP >= m_end) break;                      // uniform over the workgroup
+            bf16x8 av, bv;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int ml = ks * KSTEP + 8 * hi + j;
+                const int4 e = rowtab[ml];
+                const bool rok = e.x >= 0;
+                av[j] = (__bf16)0.f; bv[j] = (__bf16)0.f;
+                if (rok && cok) av[j] = dy16[(long)(mb + ml) * g.Cout + co];
+                const int d = e.y + tkd, h = e.z + tkh, w = e.w + tkw;
+                if (rok && kok && d >= 0 && d < g.D && h >= 0 && h < g.H && w >= 0 && w < g.W)
+                    bv[j] = x16[((((long)e.x * g.D + d) * g.H + h) * g.W + w) * g.Cin + ci];
+            }
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
+        }
+    }
+    flush_acc(acc, tot);
+    if (!kok) return;
+    const int crow0 = blockIdx.y * 32;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int c = crow0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        if (c < g.Cout) ws[((long)blockIdx.z * g.Cout + c) * K + kcol] = (float)tot[r];
+    }
+}
+
+// the partials in chunk order -> torch's [Cout, Cin, taps]
+__global__ __launch_bounds__(256) void conv3d_wgrad_sum_kernel(const float* __restrict__ ws, float* __restrict__ dw, int chunks, int Cout, int Cin,
+                                                               int taps, int accumulate) {
+    const long total = (long)Cout * Cin * taps;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;              // over [co][k = tap Cin + ci]: coalesced partial reads
+    if (i >= total) return;
+    double sd = 0.;
+    for (int z = 0; z < chunks; ++z) sd += (double)ws[(long)z * total + i];
+    const float s = (float)sd;
+    const int K = taps * Cin;
+    const int co = (int)(i / K), k = (int)(i % K), tap = k / Cin, ci = k % Cin;
+    const long o = ((long)co * Cin + ci) * taps + tap;
+    dw[o] = accumulate ? dw[o] + s : s;
+}
+
+// ------------------------------------------------------------------ MaxPool3d(3, 2, 1)
+__global__ __launch_bounds__(256) void maxpool3d_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, __bf16* __restrict__ y16,
+                                                            unsigned char* __restrict__ idx, int D, int H, int W, int C, int Do, int Ho, int Wo,
+                                                            long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;              // (((n Do + od) Ho + oh) Wo + ow) C + c
+    if (i >= total) return;
+    const int c = (int)(i % C);
+    long r = i / C;
+    const int ow = (int)(r % Wo); r /= Wo;
+    const int oh = (int)(r % Ho); r /= Ho;
+    const int od = (int)(r % Do);
+    const long n = r / Do;
+    float best = -INFINITY;
+    int bi = -1;
+    for (int a = 0; a < 3; ++a) {
+        const int d = od * 2 - 1 + a;
+        if (d < 0 || d >= D) continue;
+        for (int b = 0; b < 3; ++b) {
+            const int h = oh * 2 - 1 + b;
+            if (h < 0 || h >= H) continue;
+            for (int e = 0; e < 3; ++e) {
+                const int w = ow * 2 - 1 + e;
+                if (w < 0 || w >= W) continue;
+                const float v = x[(((n * D + d) * H + h) * W + w) * C + c];
+                // torch's scan: the first position is the start index; a value takes over when it is greater or NaN
+                if (bi < 0 || v > best || v != v) { best = v; bi = (a * 3 + b) * 3 + e; }
+            }
+        }
+    }
+    if (y) y[i] = best;
+    if (y16) y16[i] = (__bf16)best;
+    idx[i] = (unsigned char)bi;
+}
+
+__global__ __launch_bounds__(256) void maxpool3d_bwd_kernel(const float* __restrict__ dy, const unsigned char* __restrict__ idx, float* __restrict__ dx,
+                                                            __bf16* __restrict__ dx16, int D, int H, int W, int C, int Do, int Ho, int Wo, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;              // (((n D + d) H + h) W + w) C + c
+    if (i >= total) return;
+    const int c = (int)(i % C);
+    long r = i / C;
+    const int w = (int)(r % W); r /= W;
+    const int h = (int)(r % H); r /= H;
+    const int d = (int)(r % D);
+    const long n = r / D;
+    float s = 0.f;
+    for (int a = 0; a < 3; ++a) {
+        const int td = d + 1 - a;
+        if (td < 0 || (td & 1) || (td >> 1) >= Do) continue;
+        for (int b = 0; b < 3; ++b) {
+            const int th = h + 1 - b;
+            if (th < 0 || (th & 1) || (th >> 1) >= Ho) continue;
+            for (int e = 0; e < 3; ++e) {
+                const int tw = w + 1 - e;
+                if (tw < 0 || (tw & 1) || (tw >> 1) >= Wo) continue;
+                const long o = (((n * Do + (td >> 1)) * Ho + (th >> 1)) * Wo + (tw >> 1)) * C + c;
+                if (idx[o] == (a * 3 + b) * 3 + e) s += dy[o];
+            }
+        }
+    }
+    if (dx) dx[i] = s;
+    if (dx16) dx16[i] = (__bf16)s;
+}
+
+// ------------------------------------------------------------------ global average pool
+__global__ __launch_bounds__(256) void rows_mean_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, __bf16* __restrict__ y16, int S, int C,
+                                                            long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;              // n C + c
+    if (i >= total) return;
+    const long n = i / C;
+    const int c = (int)(i % C);
+    float s = 0.f;
+    for (int r = 0; r < S; ++r) s += x[(n * S + r) * C + c];
+    const float v = s / (float)S;
+    if (y) y[i] = v;
+    if (y16) y16[i] = (__bf16)v;
+}
+
+__global__ __launch_bounds__(256) void rows_mean_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, __bf16* __restrict__ dx16, int S, int C,
+                                                            long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;              // (n S + s) C + c
+    if (i >= total) return;
+    const long n = i / ((long)S * C);
+    const float v = dy[n * C + (int)(i % C)] / (float)S;
+    if (dx) dx[i] = v;
+    if (dx16) dx16[i] = (__bf16)v;
+}
+
+GatherArgs gather_args(const ConvGeo& g, bool bwd, const void* src, const void* wpk, float* out, void* out16) {
+    GatherArgs a;
+    a.src = reinterpret_cast<const __bf16*>(src); a.wpk = reinterpret_cast<const __bf16*>(wpk);
+    a.out = out; a.out16 = reinterpret_cast<__bf16*>(out16);
+    if (!bwd) { a.Ds = g.D; a.Hs = g.H; a.Ws = g.W; a.Cs = g.Cin; a.Dr = g.Do; a.Hr = g.Ho; a.Wr = g.Wo; a.M = (int)g.M; a.Nout = g.Cout; }
+    else { a.Ds = g.Do; a.Hs = g.Ho; a.Ws = g.Wo; a.Cs = g.Cout; a.Dr = g.D; a.Hr = g.H; a.Wr = g.W; a.M = (int)g.V; a.Nout = g.Cin; }
+    a.kd = g.kd; a.kh = g.kh; a.kw = g.kw; a.sd = g.sd; a.sh = g.sh; a.sw = g.sw; a.pd = g.pd; a.ph = g.ph; a.pw = g.pw;
+    a.K = g.taps * a.Cs; a.Kp = (int)kpad(a.K); a.cs_shift = shift_of(a.Cs); a.accum = 0;
+    return a;
+}
+
+int pool_geo(int N, int D, int H, int W, int C, int& Do, int& Ho, int& Wo, long& in_total, long& out_total) {
+    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0) return VITAE_ERR_INVALID_ARG;
+    Do = (D - 1) / 2 + 1; Ho = (H - 1) / 2 + 1; Wo = (W - 1) / 2 + 1;            // (X + 2 - 3) / 2 + 1
+    in_total = (long)N * D * H * W * C; out_total = (long)N * Do * Ho * Wo * C;
+    if ((long)N * D * H * W > (long)INT_MAX - 256) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    return VITAE_OK;
+}
+
+}  // namespace
+
+extern "C" long vitae_conv3d_packed_elems(int Cout, int Cin, int kd, int kh, int kw, int transposed) {
+    if (Cout <= 0 || Cin <= 0 || kd < 1 || kh < 1 || kw < 1 || kd > 7 || kh > 7 || kw > 7) return 0;
+    const long taps = (long)kd * kh * kw;
+    return transposed ? Cin * kpad(taps * Cout) : Cout * kpad(taps * Cin);
+}
+
+extern "C" int vitae_conv3d_pack_weight(const float* w, void* w16, int Cout, int Cin, int kd, int kh, int kw, int transposed, void* stream) {
+    if (!w || !w16 || Cout <= 0 || Cin <= 0) return VITAE_ERR_INVALID_ARG;
+    if (kd < 1 || kh < 1 || kw < 1 || kd > 7 || kh > 7 || kw > 7 || (Cout & 3)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    const int taps = kd * kh * kw;
+    const long Kp = kpad((long)taps * (transposed ? Cout : Cin));
+    if (Kp > (long)INT_MAX - 256) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    const long total = (long)(transposed ? Cin : Cout) * Kp;
+    hipLaunchKernelGGL(conv3d_pack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, reinterpret_cast<__bf16*>(w16), Cout, Cin,
+                       taps, (int)Kp, transposed ? 1 : 0, total);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_to_channels_last_bf16(const float* x, void* x16, int N, int C, int D, int H, int W, void* stream) {
+    if (!x || !x16 || N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return VITAE_ERR_INVALID_ARG;
+    const long S = (long)D * H * W, total = (long)N * S * C;
+    if (total > (long)INT_MAX * 128) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    hipLaunchKernelGGL(channels_last_bf16_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<__bf16*>(x16), C, S,
+                       total);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_conv3d_fwd(const void* x16, const void* w16, float* y, void* y_bf16, int N, int D, int H, int W, int Cin, int Cout, int kd,
+                                int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream) {
+    if (!x16 || !w16 || (!y && !y_bf16)) return VITAE_ERR_INVALID_ARG;
+    ConvGeo g;
+    if (const int rc = conv_geo(g, N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw)) return rc;
+    if (!aligned16({x16, w16, y, y_bf16})) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    launch_gather<false>(gather_args(g, false, x16, w16, y, y_bf16), (hipStream_t)stream);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_conv3d_bwd_input(const void* dy16, const void* w16t, float* dx, void* dx_bf16, int accumulate, int N, int D, int H, int W,
+                                      int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream) {
+    if (!dy16 || !w16t || (!dx && !dx_bf16) || (accumulate && !dx)) return VITAE_ERR_INVALID_ARG;
+    ConvGeo g;
+    if (const int rc = conv_geo(g, N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw)) return rc;
+    if (!aligned16({dy16, w16t, dx, dx_bf16})) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    GatherArgs a = gather_args(g, true, dy16, w16t, dx, dx_bf16);
+    a.accum = accumulate ? 1 : 0;
+    launch_gather<true>(a, (hipStream_t)stream);
+    return vitae_launch_status();
+}
+
+extern "C" long vitae_conv3d_wgrad_ws_floats(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd,
+                                             int ph, int pw) {
+    ConvGeo g;
+    if (conv_geo(g, N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw)) return 0;
+    return (long)cdiv(g.M, WCHUNK) * Cout * g.K;
+}
+
+extern "C" int vitae_conv3d_bwd_weight(const void* dy16, const void* x16, float* dw, float* ws, long ws_floats, int accumulate, int N, int D, int H,
+                                       int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
+                                       void* stream) {
+    if (!dy16 || !x16 || !dw || !ws) return VITAE_ERR_INVALID_ARG;
+    ConvGeo g;
+    if (const int rc = conv_geo(g, N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw)) return rc;
+    const int chunks = cdiv(g.M, WCHUNK);
+    if (ws_floats < (long)chunks * Cout * g.K) return VITAE_ERR_INVALID_ARG;
+    if (chunks > 65535) return VITAE_ERR_UNSUPPORTED_SHAPE;                     // grid.z
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(conv3d_wgrad_part_kernel, dim3(cdiv(g.K, 128), cdiv(Cout, 32), chunks), dim3(256), 0, st,
+                       reinterpret_cast<const __bf16*>(dy16), reinterpret_cast<const __bf16*>(x16), ws, g);
+    const long total = (long)Cout * g.K;
+    hipLaunchKernelGGL(conv3d_wgrad_sum_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, ws, dw, chunks, Cout, Cin, g.taps, accumulate ? 1 : 0);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_maxpool3d_fwd(const float* x, float* y, void* y_bf16, void* idx, int N, int D, int H, int W, int C, void* stream) {
+    if (!x || (!y && !y_bf16) || !idx) return VITAE_ERR_INVALID_ARG;
+    int Do, Ho, Wo;
+    long in_total, out_total;
+    if (const int rc = pool_geo(N, D, H, W, C, Do, Ho, Wo, in_total, out_total)) return rc;
+    hipLaunchKernelGGL(maxpool3d_fwd_kernel, dim3(cdiv(out_total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, reinterpret_cast<__bf16*>(y_bf16),
+                       reinterpret_cast<unsigned char*>(idx), D, H, W, C, Do, Ho, Wo, out_total);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_maxpool3d_bwd(const float* dy, const void* idx, float* dx, void* dx_bf16, int N, int D, int H, int W, int C, void* stream) {
+    if (!dy || !idx || (!dx && !dx_bf16)) return VITAE_ERR_INVALID_ARG;
+    int Do, Ho, Wo;
+    long in_total, out_total;
+    if (const int rc = pool_geo(N, D, H, W, C, Do, Ho, Wo, in_total, out_total)) return rc;
+    hipLaunchKernelGGL(maxpool3d_bwd_kernel, dim3(cdiv(in_total, 256)), dim3(256), 0, (hipStream_t)stream, dy,
+                       reinterpret_cast<const unsigned char*>(idx), dx, reinterpret_cast<__bf16*>(dx_bf16), D, H, W, C, Do, Ho, Wo, in_total);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_rows_mean_fwd(const float* x, float* y, void* y_bf16, int N, int S, int C, void* stream) {
+    if (!x || (!y && !y_bf16) || N <= 0 || S <= 0 || C <= 0) return VITAE_ERR_INVALID_ARG;
+    const long total = (long)N * C;
+    hipLaunchKernelGGL(rows_mean_fwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, reinterpret_cast<__bf16*>(y_bf16), S, C,
+                       total);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_rows_mean_bwd(const float* dy, float* dx, void* dx_bf16, int N, int S, int C, void* stream) {
+    if (!dy || (!dx && !dx_bf16) || N <= 0 || S <= 0 || C <= 0) return VITAE_ERR_INVALID_ARG;
+    const long total = (long)N * S * C;
+    if (total > (long)INT_MAX * 128) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    hipLaunchKernelGGL(rows_mean_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, dy, dx, reinterpret_cast<__bf16*>(dx_bf16), S, C,
+                       total);
+    return vitae_launch_status();
+}

@@ -791,7 +791,10 @@ __global__ __launch_bounds__(256) void bn1d_stats_part_kernel(const float* __res
     }
 }
 
-__global__ __launch_bounds__(256) void bn1d_relu_apply_part_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+// RELU / RES (ABI 56, the BasicBlock tail of the 3-D ResNet): y = [relu](bn(x) [+ res]); <true, false> is the predictor's BN + ReLU
+template <bool RELU, bool RES>
+__global__ __launch_bounds__(256) void bn1d_relu_apply_part_kernel(const float* __restrict__ x, const float* __restrict__ res,
+                                                                   const float* __restrict__ w, const float* __restrict__ b,
                                                                    const float* __restrict__ part, float* __restrict__ y, __bf16* __restrict__ y16,
                                                                    float* __restrict__ save_mean, float* __restrict__ save_rstd,
                                                                    float* __restrict__ run_mean, float* __restrict__ run_var,
@@ -833,8 +836,11 @@ __global__ __launch_bounds__(256) void bn1d_relu_apply_part_kernel(const float* 
     bn_split_rows(sp, R, r0, r1);
     for (int r = r0 + rg; r < r1; r += BN_RG) {
         f32x4 v = ((*reinterpret_cast<const f32x4*>(x + (long)r * D + c) - mean0) - corr) * sc + be;
+        if (RES) v += *reinterpret_cast<const f32x4*>(res + (long)r * D + c);
+        if (RELU) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+        }
         *reinterpret_cast<f32x4*>(y + (long)r * D + c) = v;
         if (y16) {
             bf16x4 h;
@@ -857,6 +863,7 @@ __global__ __launch_bounds__(256) void bn1d_relu_apply_part_kernel(const float* 
     }
 }
 
+template <bool RELU>
 __global__ __launch_bounds__(256) void bn1d_relu_bwd_sums_part_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ y,
                                                                       const float* __restrict__ save_mean, const float* __restrict__ save_rstd,
                                                                       float* __restrict__ part, int R, int D, const BnSplit sp) {
@@ -872,7 +879,8 @@ __global__ __launch_bounds__(256) void bn1d_relu_bwd_sums_part_kernel(const floa
     if (ok)
         for (int r = r0 + rg; r < r1; r += BN_RG) {
             const long i = (long)r * D + c;
-            const f32x4 yv = *reinterpret_cast<const f32x4*>(y + i), dv = *reinterpret_cast<const f32x4*>(dy + i), xv = *reinterpret_cast<const f32x4*>(x + i);
+            const f32x4 yv = RELU ? *reinterpret_cast<const f32x4*>(y + i) : f32x4{1.f, 1.f, 1.f, 1.f};
+            const f32x4 dv = *reinterpret_cast<const f32x4*>(dy + i), xv = *reinterpret_cast<const f32x4*>(x + i);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float d = yv[e] > 0.f ? dv[e] : 0.f;
@@ -887,11 +895,13 @@ __global__ __launch_bounds__(256) void bn1d_relu_bwd_sums_part_kernel(const floa
     }
 }
 
+// RELU = false: dy is the gradient of bn(x) [+ res] itself (y is not read); dres (optional) receives the masked gradient
+template <bool RELU>
 __global__ __launch_bounds__(256) void bn1d_relu_bwd_apply_part_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ y,
                                                                        const float* __restrict__ w, const float* __restrict__ save_mean,
                                                                        const float* __restrict__ save_rstd, const float* __restrict__ part,
-                                                                       float* __restrict__ dx, __bf16* __restrict__ dx16, float* __restrict__ dw,
-                                                                       float* __restrict__ db, int R, int D, const BnSplit sp) {
+                                                                       float* __restrict__ dx, __bf16* __restrict__ dx16, float* __restrict__ dres,
+                                                                       float* __restrict__ dw, float* __restrict__ db, int R, int D, const BnSplit sp) {
     const int cg = threadIdx.x % BN_CG, rg = threadIdx.x / BN_CG;
     const int c = blockIdx.x * BN_COLS + 4 * cg;
     if (c >= D) return;
@@ -912,13 +922,16 @@ __global__ __launch_bounds__(256) void bn1d_relu_bwd_apply_part_kernel(const flo
     bn_split_rows(sp, R, r0, r1);
     for (int r = r0 + rg; r < r1; r += BN_RG) {
         const long i = (long)r * D + c;
-        const f32x4 yv = *reinterpret_cast<const f32x4*>(y + i), dv = *reinterpret_cast<const f32x4*>(dy + i), xv = *reinterpret_cast<const f32x4*>(x + i);
-        f32x4 o;
+        const f32x4 yv = RELU ? *reinterpret_cast<const f32x4*>(y + i) : f32x4{1.f, 1.f, 1.f, 1.f};
+        const f32x4 dv = *reinterpret_cast<const f32x4*>(dy + i), xv = *reinterpret_cast<const f32x4*>(x + i);
+        f32x4 o, dm;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float d = yv[e] > 0.f ? dv[e] : 0.f;
+            dm[e] = d;
             o[e] = g[e] * rstd[e] * (d - m1[e] - (xv[e] - mean[e]) * rstd[e] * m2[e]);
         }
+        if (dres) *reinterpret_cast<f32x4*>(dres + i) = dm;
         *reinterpret_cast<f32x4*>(dx + i) = o;
         if (dx16) {
             bf16x4 h;
@@ -926,6 +939,34 @@ __global__ __launch_bounds__(256) void bn1d_relu_bwd_apply_part_kernel(const flo
             for (int e = 0; e < 4; ++e) h[e] = (__bf16)o[e];
             *reinterpret_cast<bf16x4*>(dx16 + i) = h;
         }
+    }
+}
+
+// eval mode of the BasicBlock tail: y = [relu]((x - running_mean) / sqrt(running_var + eps) * w + b [+ res]), four columns a thread
+__global__ __launch_bounds__(256) void bn_tail_eval_kernel(const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ w,
+                                                           const float* __restrict__ b, const float* __restrict__ run_mean,
+                                                           const float* __restrict__ run_var, float* __restrict__ y, __bf16* __restrict__ y16,
+                                                           long n4, int D, float eps, int relu) {
+    const long i4 = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i4 >= n4) return;
+    const long i = i4 * 4;
+    const int c = (int)(i % D);                              // D % 4 == 0: the four share a row
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i), m = *reinterpret_cast<const f32x4*>(run_mean + c);
+    const f32x4 var = *reinterpret_cast<const f32x4*>(run_var + c), g = *reinterpret_cast<const f32x4*>(w + c), be = *reinterpret_cast<const f32x4*>(b + c);
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (xv[e] - m[e]) * rsqrtf(var[e] + eps) * g[e] + be[e];
+    if (res) v += *reinterpret_cast<const f32x4*>(res + i);
+    if (relu) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+    }
+    if (y) *reinterpret_cast<f32x4*>(y + i) = v;
+    if (y16) {
+        bf16x4 h;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) h[e] = (__bf16)v[e];
+        *reinterpret_cast<bf16x4*>(y16 + i) = h;
     }
 }
 
@@ -1176,7 +1217,8 @@ extern "C" int vitae_bn1d_relu_fwd_split(const float* x, const float* w, const f
     const BnSplit sp = bn_split_plan(R, D);
     const dim3 grid(cdiv(D, BN_COLS), sp.RS);
     hipLaunchKernelGGL(bn1d_stats_part_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, ws, R, D, sp);
-    hipLaunchKernelGGL(bn1d_relu_apply_part_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, w, b, ws, y, reinterpret_cast<__bf16*>(y_bf16),
+    hipLaunchKernelGGL((bn1d_relu_apply_part_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, x, (const float*)nullptr, w, b, ws, y,
+                       reinterpret_cast<__bf16*>(y_bf16),
                        save_mean, save_rstd, running_mean, running_var, num_batches_tracked, R, D, eps, momentum, sp);
     return vitae_launch_status();
 }
@@ -1188,8 +1230,61 @@ extern "C" int vitae_bn1d_relu_bwd_split(const float* dy, const float* x, const 
     if (!bn_vec_ok(D, {dy, x, y, w, save_mean, save_rstd, dx, ws}) || ((uintptr_t)dx_bf16 & 7)) return VITAE_ERR_UNSUPPORTED_SHAPE;
     const BnSplit sp = bn_split_plan(R, D);
     const dim3 grid(cdiv(D, BN_COLS), sp.RS);
-    hipLaunchKernelGGL(bn1d_relu_bwd_sums_part_kernel, grid, dim3(256), 0, (hipStream_t)stream, dy, x, y, save_mean, save_rstd, ws, R, D, sp);
-    hipLaunchKernelGGL(bn1d_relu_bwd_apply_part_kernel, grid, dim3(256), 0, (hipStream_t)stream, dy, x, y, w, save_mean, save_rstd, ws, dx,
-                       reinterpret_cast<__bf16*>(dx_bf16), dw, db, R, D, sp);
+    hipLaunchKernelGGL(bn1d_relu_bwd_sums_part_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, dy, x, y, save_mean, save_rstd, ws, R, D, sp);
+    hipLaunchKernelGGL(bn1d_relu_bwd_apply_part_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, dy, x, y, w, save_mean, save_rstd, ws, dx,
+                       reinterpret_cast<__bf16*>(dx_bf16), (float*)nullptr, dw, db, R, D, sp);
+    return vitae_launch_status();
+}
+
+// ---- the BasicBlock tail of the 3-D ResNet (ABI 56): y = [relu](bn(x) [+ res]) on channels-last rows, on the split machinery above
+extern "C" int vitae_bn_tail_fwd_split(const float* x, const float* res, const float* w, const float* b, float* y, void* y_bf16, float* save_mean,
+                                       float* save_rstd, float* running_mean, float* running_var, long long* num_batches_tracked, int R, int C,
+                                       float eps, float momentum, int relu, float* ws, void* stream) {
+    if (!x || !w || !b || !y || !save_mean || !save_rstd || !ws || R <= 0 || C <= 0) return VITAE_ERR_INVALID_ARG;
+    if (!bn_vec_ok(C, {x, res, w, b, y, save_mean, save_rstd, ws}) || ((uintptr_t)y_bf16 & 7)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (!running_mean) num_batches_tracked = nullptr;
+    else if (!running_var) return VITAE_ERR_INVALID_ARG;
+    const BnSplit sp = bn_split_plan(R, C);
+    const dim3 grid(cdiv(C, BN_COLS), sp.RS);
+    const hipStream_t st = (hipStream_t)stream;
+    __bf16* y16 = reinterpret_cast<__bf16*>(y_bf16);
+    hipLaunchKernelGGL(bn1d_stats_part_kernel, grid, dim3(256), 0, st, x, ws, R, C, sp);
+#define VITAE_BN_TAIL(RELU, RES)                                                                                                        \
+    hipLaunchKernelGGL((bn1d_relu_apply_part_kernel<RELU, RES>), grid, dim3(256), 0, st, x, res, w, b, ws, y, y16, save_mean, save_rstd, \
+                       running_mean, running_var, num_batches_tracked, R, C, eps, momentum, sp)
+    if (relu && res) VITAE_BN_TAIL(true, true);
+    else if (relu) VITAE_BN_TAIL(true, false);
+    else if (res) VITAE_BN_TAIL(false, true);
+    else VITAE_BN_TAIL(false, false);
+#undef VITAE_BN_TAIL
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_bn_tail_eval(const float* x, const float* res, const float* w, const float* b, const float* running_mean,
+                                  const float* running_var, float* y, void* y_bf16, int R, int C, float eps, int relu, void* stream) {
+    if (!x || !w || !b || !running_mean || !running_var || (!y && !y_bf16) || R <= 0 || C <= 0) return VITAE_ERR_INVALID_ARG;
+    if (!bn_vec_ok(C, {x, res, w, b, running_mean, running_var, y}) || ((uintptr_t)y_bf16 & 7)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    const long n4 = (long)R * C / 4;
+    hipLaunchKernelGGL(bn_tail_eval_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, (hipStream_t)stream, x, res, w, b, running_mean, running_var, y,
+                       reinterpret_cast<__bf16*>(y_bf16), n4, C, eps, relu ? 1 : 0);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_bn_tail_bwd_split(const float* dy, const float* x, const float* y, const float* w, const float* save_mean,
+                                       const float* save_rstd, float* dx, void* dx_bf16, float* dres, float* dw, float* db, int R, int C,
+                                       int relu, float* ws, void* stream) {
+    if (!dy || !x || (relu && !y) || !w || !save_mean || !save_rstd || !dx || !dw || !db || !ws || R <= 0 || C <= 0) return VITAE_ERR_INVALID_ARG;
+    if (!bn_vec_ok(C, {dy, x, y, w, save_mean, save_rstd, dx, dres, ws}) || ((uintptr_t)dx_bf16 & 7)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    const BnSplit sp = bn_split_plan(R, C);
+    const dim3 grid(cdiv(C, BN_COLS), sp.RS);
+    const hipStream_t st = (hipStream_t)stream;
+    __bf16* dx16 = reinterpret_cast<__bf16*>(dx_bf16);
+    if (relu) {
+        hipLaunchKernelGGL(bn1d_relu_bwd_sums_part_kernel<true>, grid, dim3(256), 0, st, dy, x, y, save_mean, save_rstd, ws, R, C, sp);
+        hipLaunchKernelGGL(bn1d_relu_bwd_apply_part_kernel<true>, grid, dim3(256), 0, st, dy, x, y, w, save_mean, save_rstd, ws, dx, dx16, dres, dw, db, R, C, sp);
+    } else {
+        hipLaunchKernelGGL(bn1d_relu_bwd_sums_part_kernel<false>, grid, dim3(256), 0, st, dy, x, y, save_mean, save_rstd, ws, R, C, sp);
+        hipLaunchKernelGGL(bn1d_relu_bwd_apply_part_kernel<false>, grid, dim3(256), 0, st, dy, x, y, w, save_mean, save_rstd, ws, dx, dx16, dres, dw, db, R, C, sp);
+    }
     return vitae_launch_status();
 }

@@ -1,0 +1,220 @@
+"""Launch sequences of the 3-D ResNet baseline (k_fold_training_scripts/resnet_3d.py) on the kernels of csrc/conv3d.hip and the
+BasicBlock tail of csrc/norm.hip: one forward per route — inference on running statistics, training with what the backward needs
+kept — and the backward in reverse order.  The counterpart of encoder.py for the convolutional baseline.
+
+Inside the network every activation is channels-last rows ``[N D H W, C]``; operands of the convolutions are bf16, what a
+BatchNorm reads (the convolution's output) and what a residual adds are fp32.  Launch order of one BasicBlock:
+
+  forward    conv1 -> bn1 + relu -> conv2 -> [downsample conv -> bn] -> bn2 + residual + relu
+  backward   bn2 tail (dx, dres) -> conv2 dW, dX -> bn1 tail -> conv1 dW -> [downsample bn -> dW -> dX] -> conv1 dX (added to the
+             residual branch's gradient)
+
+Kept per block for the backward: the bf16 input of each convolution, the fp32 output of each convolution (what BatchNorm
+normalises), the fp32 outputs of the two ReLUs (their masks; the block output is also the next block's residual), mean / rstd.
+Nothing here falls back to torch operators: a missing kernel is an error.
+"""
+import torch
+
+from ._abi import VitaeError, lib
+
+BF16, F32 = torch.bfloat16, torch.float32
+
+
+def _st(t):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _param(t, what):
+    if not t.is_cuda or t.dtype != F32:
+        raise VitaeError(f'{what} must be an fp32 tensor on the MI355X (is {t.dtype} on {t.device}); there is no CPU fallback')
+    return t.detach().contiguous()
+
+
+def _geo(N, vol, conv):
+    return (N, *vol, conv.in_channels, conv.out_channels, *conv.kernel_size, *conv.stride, *conv.padding)
+
+
+def conv_out_vol(vol, conv):
+    return tuple((vol[i] + 2 * conv.padding[i] - conv.kernel_size[i]) // conv.stride[i] + 1 for i in range(3))
+
+
+def pack_weight(conv, transposed):
+    w = _param(conv.weight, 'a convolution weight')
+    n = lib.vitae_conv3d_packed_elems(conv.out_channels, conv.in_channels, *conv.kernel_size, transposed)
+    out = torch.empty(n, dtype=BF16, device=w.device)
+    lib.vitae_conv3d_pack_weight(w.data_ptr(), out.data_ptr(), conv.out_channels, conv.in_channels, *conv.kernel_size, transposed, _st(w))
+    return out
+
+
+def conv_fwd(x16, N, vol, conv):
+    """-> fp32 [M, Cout], output volume"""
+    ovol = conv_out_vol(vol, conv)
+    y = torch.empty(N * ovol[0] * ovol[1] * ovol[2], conv.out_channels, dtype=F32, device=x16.device)
+    lib.vitae_conv3d_fwd(x16.data_ptr(), pack_weight(conv, 0).data_ptr(), y.data_ptr(), None, *_geo(N, vol, conv), _st(x16))
+    return y, ovol
+
+
+def conv_bwd_input(dy16, N, vol, conv, into=None):
+    """dx fp32 [N D H W, Cin]; `into`: the sum is added to that tensor (the residual branch's gradient) instead"""
+    dx = into if into is not None else torch.empty(N * vol[0] * vol[1] * vol[2], conv.in_channels, dtype=F32, device=dy16.device)
+    lib.vitae_conv3d_bwd_input(dy16.data_ptr(), pack_weight(conv, 1).data_ptr(), dx.data_ptr(), None, 0 if into is None else 1,
+                               *_geo(N, vol, conv), _st(dy16))
+    return dx
+
+
+def conv_bwd_weight(dy16, x16, N, vol, conv):
+    geo = _geo(N, vol, conv)
+    n = lib.vitae_conv3d_wgrad_ws_floats(*geo)
+    ws = torch.empty(n, dtype=F32, device=dy16.device)
+    dw = torch.empty_like(conv.weight, dtype=F32, memory_format=torch.contiguous_format)
+    lib.vitae_conv3d_bwd_weight(dy16.data_ptr(), x16.data_ptr(), dw.data_ptr(), ws.data_ptr(), n, 0, *geo, _st(dy16))
+    return dw
+
+
+def _bn_operands(bn):
+    if bn.momentum is None or not bn.affine or not bn.track_running_stats:
+        raise NotImplementedError('BatchNorm3d: only affine layers with running statistics and a fixed momentum are built')
+    return _param(bn.weight, 'a BatchNorm weight'), _param(bn.bias, 'a BatchNorm bias')
+
+
+def bn_tail_train(x, res, bn, relu, want16):
+    """y = [relu](bn(x) [+ res]) on batch statistics; updates the running statistics -> y, y16 | None, mean, rstd"""
+    R, C = x.shape
+    w, b = _bn_operands(bn)
+    y = torch.empty_like(x)
+    y16 = torch.empty(R, C, dtype=BF16, device=x.device) if want16 else None
+    mean, rstd = torch.empty(C, dtype=F32, device=x.device), torch.empty(C, dtype=F32, device=x.device)
+    ws = torch.empty(lib.vitae_bn1d_split_ws_floats(R, C), dtype=F32, device=x.device)
+    lib.vitae_bn_tail_fwd_split(x.data_ptr(), _p(res), w.data_ptr(), b.data_ptr(), y.data_ptr(), _p(y16), mean.data_ptr(), rstd.data_ptr(),
+                                bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr(), R, C, bn.eps,
+                                bn.momentum, relu, ws.data_ptr(), _st(x))
+    return y, y16, mean, rstd
+
+
+def bn_tail_eval(x, res, bn, relu, want16):
+    R, C = x.shape
+    w, b = _bn_operands(bn)
+    y = torch.empty_like(x)
+    y16 = torch.empty(R, C, dtype=BF16, device=x.device) if want16 else None
+    lib.vitae_bn_tail_eval(x.data_ptr(), _p(res), w.data_ptr(), b.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), y.data_ptr(),
+                           _p(y16), R, C, bn.eps, relu, _st(x))
+    return y, y16
+
+
+def bn_tail_bwd(dy, x, y, bn, mean, rstd, relu, dres=None):
+    """-> dx16 (the next convolution gradient's operand), dw, db; dres (optional) receives the masked gradient"""
+    R, C = x.shape
+    w, _ = _bn_operands(bn)
+    dx = torch.empty_like(x)
+    dx16 = torch.empty(R, C, dtype=BF16, device=x.device)
+    dw, db = torch.zeros(C, dtype=F32, device=x.device), torch.zeros(C, dtype=F32, device=x.device)       # the kernel adds to them
+    ws = torch.empty(lib.vitae_bn1d_split_ws_floats(R, C), dtype=F32, device=x.device)
+    lib.vitae_bn_tail_bwd_split(dy.data_ptr(), x.data_ptr(), _p(y) if relu else None, w.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
+                                dx16.data_ptr(), _p(dres), dw.data_ptr(), db.data_ptr(), R, C, relu, ws.data_ptr(), _st(x))
+    return dx16, dw, db
+
+
+class HipResNetRunner:
+    """Sequences the kernels over a ``k_fold_training_scripts.resnet_3d.ResNet`` (its modules hold the parameters and buffers)."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def blocks(self):
+        for li in range(1, 5):
+            for bi, blk in enumerate(getattr(self.model, f'layer{li}')):
+                yield f'layer{li}.{bi}', blk
+
+    # ------------------------------------------------------------------ forward
+    def _forward(self, x, train):
+        """-> features fp32 [N, C] and (train) what the backward needs"""
+        m = self.model
+        if not x.is_cuda:
+            raise VitaeError(f'ResNet: input is on {x.device}; this package computes on MI355X only (no CPU fallback).')
+        if x.dim() != 5 or x.shape[1] != m.conv1.in_channels:
+            raise VitaeError(f'ResNet: expected [N, {m.conv1.in_channels}, D, H, W], got {tuple(x.shape)}')
+        bn = bn_tail_train if train else (lambda x_, res, bn_, relu, want16: bn_tail_eval(x_, res, bn_, relu, want16) + (None, None))
+        x = x.detach().contiguous().float()
+        N, C, vol0 = x.shape[0], x.shape[1], tuple(x.shape[2:])
+        st = _st(x)
+        x16 = torch.empty(N * vol0[0] * vol0[1] * vol0[2], C, dtype=BF16, device=x.device)
+        lib.vitae_to_channels_last_bf16(x.data_ptr(), x16.data_ptr(), N, C, *vol0, st)
+        pre, vol = conv_fwd(x16, N, vol0, m.conv1)
+        y, y16, mean, rstd = bn(pre, None, m.bn1, 1, m.no_max_pool)
+        stem = dict(x16=x16, vol_in=vol0, pre=pre, y=y, mean=mean, rstd=rstd, vol=vol, idx=None)
+        cur, cur16 = y, y16
+        if not m.no_max_pool:
+            C0 = y.shape[1]
+            pvol = tuple((v - 1) // 2 + 1 for v in vol)
+            rows = N * pvol[0] * pvol[1] * pvol[2]
+            cur, cur16 = torch.empty(rows, C0, dtype=F32, device=x.device), torch.empty(rows, C0, dtype=BF16, device=x.device)
+            idx = torch.empty(rows, C0, dtype=torch.uint8, device=x.device)
+            lib.vitae_maxpool3d_fwd(y.data_ptr(), cur.data_ptr(), cur16.data_ptr(), idx.data_ptr(), N, *vol, C0, st)
+            stem['idx'], vol = idx, pvol
+        recs = []
+        for _, blk in self.blocks():
+            pre1, ovol = conv_fwd(cur16, N, vol, blk.conv1)
+            y1, y1_16, mean1, rstd1 = bn(pre1, None, blk.bn1, 1, True)
+            pre2, _ = conv_fwd(y1_16, N, ovol, blk.conv2)
+            rec = dict(in16=cur16, vol_in=vol, vol=ovol, pre1=pre1, y1=y1, y1_16=y1_16, mean1=mean1, rstd1=rstd1, pre2=pre2)
+            if blk.downsample is not None:
+                pred, _ = conv_fwd(cur16, N, vol, blk.downsample[0])
+                res, _, meand, rstdd = bn(pred, None, blk.downsample[1], 0, False)
+                rec.update(pred=pred, meand=meand, rstdd=rstdd)
+            else:
+                res = cur
+            cur, cur16, mean2, rstd2 = bn(pre2, res, blk.bn2, 1, True)
+            rec.update(out=cur, mean2=mean2, rstd2=rstd2)
+            recs.append(rec)
+            vol = ovol
+        S, Cl = vol[0] * vol[1] * vol[2], cur.shape[1]
+        feat = torch.empty(N, Cl, dtype=F32, device=x.device)
+        lib.vitae_rows_mean_fwd(cur.data_ptr(), feat.data_ptr(), None, N, S, Cl, st)
+        return feat, (dict(N=N, S=S, stem=stem, recs=recs) if train else None)
+
+    def infer(self, x):
+        return self._forward(x, False)[0]
+
+    def forward_keep(self, x):
+        return self._forward(x, True)
+
+    # ------------------------------------------------------------------ backward
+    def backward(self, kept, dfeat):
+        """-> {parameter name: gradient} of everything below the head; the input volume gets none"""
+        m, N, S = self.model, kept['N'], kept['S']
+        grads = {}
+        dfeat = dfeat.contiguous().float()
+        Cl = dfeat.shape[1]
+        dcur = torch.empty(N * S, Cl, dtype=F32, device=dfeat.device)
+        lib.vitae_rows_mean_bwd(dfeat.data_ptr(), dcur.data_ptr(), None, N, S, Cl, _st(dfeat))
+        for (name, blk), rec in reversed(list(zip(self.blocks(), kept['recs']))):
+            vin, vout = rec['vol_in'], rec['vol']
+            identity = blk.downsample is None
+            dres = torch.empty_like(rec['out'])                        # identity shortcut: this IS the block input's gradient buffer
+            d2_16, grads[f'{name}.bn2.weight'], grads[f'{name}.bn2.bias'] = bn_tail_bwd(dcur, rec['pre2'], rec['out'], blk.bn2, rec['mean2'],
+                                                                                      rec['rstd2'], 1, dres)
+            grads[f'{name}.conv2.weight'] = conv_bwd_weight(d2_16, rec['y1_16'], N, vout, blk.conv2)
+            dy1 = conv_bwd_input(d2_16, N, vout, blk.conv2)
+            d1_16, grads[f'{name}.bn1.weight'], grads[f'{name}.bn1.bias'] = bn_tail_bwd(dy1, rec['pre1'], rec['y1'], blk.bn1, rec['mean1'],
+                                                                                      rec['rstd1'], 1)
+            grads[f'{name}.conv1.weight'] = conv_bwd_weight(d1_16, rec['in16'], N, vin, blk.conv1)
+            if identity:
+                din = dres
+            else:
+                dd_16, grads[f'{name}.downsample.1.weight'], grads[f'{name}.downsample.1.bias'] = bn_tail_bwd(
+                    dres, rec['pred'], None, blk.downsample[1], rec['meand'], rec['rstdd'], 0)
+                grads[f'{name}.downsample.0.weight'] = conv_bwd_weight(dd_16, rec['in16'], N, vin, blk.downsample[0])
+                din = conv_bwd_input(dd_16, N, vin, blk.downsample[0])
+            dcur = conv_bwd_input(d1_16, N, vin, blk.conv1, into=din)
+        stem = kept['stem']
+        if stem['idx'] is not None:
+            dy = torch.empty_like(stem['y'])
+            lib.vitae_maxpool3d_bwd(dcur.data_ptr(), stem['idx'].data_ptr(), dy.data_ptr(), None, N, *stem['vol'], dy.shape[1], _st(dy))
+            dcur = dy
+        d16, grads['bn1.weight'], grads['bn1.bias'] = bn_tail_bwd(dcur, stem['pre'], stem['y'], m.bn1, stem['mean'], stem['rstd'], 1)
+        grads['conv1.weight'] = conv_bwd_weight(d16, stem['x16'], N, stem['vol_in'], m.conv1)      # the input volume has no gradient
+        return grads
