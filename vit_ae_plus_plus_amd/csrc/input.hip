@@ -38,10 +38,13 @@ __global__ __launch_bounds__(256) void norm_stats_kernel(const float* __restrict
     const f32x4* x4 = reinterpret_cast<const f32x4*>(xg);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const f32x4 v = x4[i];
-        float ps = 0.f, pq = 0.f;
+        // every element widened before it is added or squared, as in the scalar loop below: an fp32 partial sum of four squares
+        // rounds at 2^-24 mean^2, which the variance's sum_q - sum * mean amplifies by (mean / std)^2
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { ps += v[e]; pq += v[e] * v[e]; lo = fminf(lo, v[e]); hi = fmaxf(hi, v[e]); }
-        s += (double)ps; q += (double)pq;
+        for (int e = 0; e < 4; ++e) {
+            const double d = (double)v[e];
+            s += d; q += d * d; lo = fminf(lo, v[e]); hi = fmaxf(hi, v[e]);
+        }
     }
     for (long i = n4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float v = xg[i];
@@ -67,21 +70,29 @@ __global__ __launch_bounds__(256) void norm_stats_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                          const double* __restrict__ ws, long n, int mode) {
     const int g = blockIdx.y;
-    float sub, mul, add = 0.f;
+    const float* xg = x + (long)g * n;
+    float* yg = y + (long)g * n;
     if (mode == VITAE_NORM_ZSCORE) {
         const double mean = ws[3 * g] / (double)n;
         const double var = (ws[3 * g + 1] - ws[3 * g] * mean) / (double)(n - 1);      // unbiased, as torch.var
-        sub = (float)mean; mul = (float)(1.0 / sqrt(var));
-    } else {
+        float sub = (float)mean, mul = (float)(1.0 / sqrt(var));
+        // a constant group is the reference's 0 / 0 whatever round-off sum_q - sum * mean is left with for a c that is no small integer
         const unsigned int* mm = reinterpret_cast<const unsigned int*>(ws + 3 * g + 2);
-        const float lo = key_float(mm[0]), hi = key_float(mm[1]);
-        sub = lo; mul = 1.f / (hi - lo);
-        if (mode == VITAE_NORM_MINMAX_PM1) { mul *= 2.f; add = -1.f; }
+        if (mm[0] == mm[1]) { sub = key_float(mm[0]); mul = INFINITY; }
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) yg[i] = (xg[i] - sub) * mul;
+        return;
     }
-    const float* xg = x + (long)g * n;
-    float* yg = y + (long)g * n;
+    // min-max: the reference's own statement, (x - lo) / (hi - lo), with a correctly rounded division.  x - lo <= hi - lo after
+    // rounding too, so the quotient never leaves [0, 1], lo maps to 0 and hi to 1 exactly (a multiplication by 1 / (hi - lo)
+    // overshoots 1 for about one range in seven); 2 q - 1 is exact in q's last place.
+    const unsigned int* mm = reinterpret_cast<const unsigned int*>(ws + 3 * g + 2);
+    float lo = key_float(mm[0]);
+    const float den = key_float(mm[1]) - lo;
+    // fminf / fmaxf skip a NaN voxel; the sum does not.  torch.min / torch.max return NaN then, and the whole group with it.
+    if (ws[3 * g] != ws[3 * g]) lo = __uint_as_float(0x7fc00000u);
+    const float two = mode == VITAE_NORM_MINMAX_PM1 ? 2.f : 1.f, add = mode == VITAE_NORM_MINMAX_PM1 ? -1.f : 0.f;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
-        yg[i] = (xg[i] - sub) * mul + add;
+        yg[i] = two * ((xg[i] - lo) / den) + add;
 }
 
 // ---- augmentations of the pre-training scripts (k_fold_cross_valid_combined_brats.py:93-97: torchio RandomAffine ->

@@ -12,7 +12,7 @@
 namespace {
 
 // ---------------------------------------------------------------- masking
-// rank[i] = #{j : noise[j] < noise[i] or (== and j < i)} is the stable ascending argsort position, so
+// rank[i] = #{j : noise[j] before noise[i], or tied with it and j < i} is the stable ascending argsort position (NaN last), so
 // ids_restore[i] = rank[i] (= argsort(argsort(noise))), ids_shuffle[rank[i]] = i and mask[i] = rank[i] >= len_keep (0 = keep,
 // 1 = remove).  A workgroup owns 32 elements of one sample; eight lanes share an element (each compares it with every eighth j,
 // the row sitting in LDS) and fold their counts with three shuffles.  (One workgroup per SAMPLE, one element per thread and
@@ -28,10 +28,14 @@ __global__ __launch_bounds__(256) void random_masking_kernel(const float* __rest
     const int i = blockIdx.x * 32 + (threadIdx.x >> 3), part = threadIdx.x & 7;
     const bool live = i < L;
     const float v = nz[live ? i : 0];
+    // torch.argsort's total order: a NaN sorts behind every number and NaNs tie with each other, so the ranks are a permutation
+    // for any noise (with `u < v || (u == v && j < i)` alone every NaN got rank 0 and entries of ids_shuffle stayed unwritten)
+    const bool vnan = v != v;
     int rank = 0;
     for (int j = part; j < L; j += 8) {
         const float u = nz[j];
-        rank += (u < v) || (u == v && j < i);
+        const bool unan = u != u;
+        rank += (u < v) || (vnan && !unan) || ((u == v || (unan && vnan)) && j < i);
     }
     rank += __shfl_xor(rank, 1, 64);
     rank += __shfl_xor(rank, 2, 64);
