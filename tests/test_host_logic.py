@@ -215,3 +215,24 @@ def test_bench_options():
     assert a.full and a.dump_outputs == 'out'
     with pytest.raises(SystemExit):
         bench.parse(['--steps', '0'])
+
+
+def test_fit_split_shrinks_to_capacity_and_caches_per_key():
+    """_launch.fit_split: the planner's proposal lowered until its scratch fits (never below 1), one planner call per key, and the
+    GELU rule as the engine's call sites apply it — outside the cache, so a cached split never depends on the epilogue."""
+    from vit_ae_plus_plus_amd._launch import EPI_GELU, EPI_NONE, fit_split
+    cache, calls = {}, []
+
+    def pick(v):
+        return lambda: (calls.append(v), v)[1]
+
+    need = lambda s: 100 * s
+    assert fit_split(cache, 'a', pick(7), need, 350) == 3 and cache == {'a': 3}
+    assert fit_split({}, 'a', pick(7), need, 99) == 1            # capacity below need(1): one split, no further
+    assert fit_split({}, 'a', pick(2), need, 10 ** 6) == 2       # what fits is left alone
+    calls.clear()
+    split = lambda key, v: cache.get(key) or fit_split(cache, key, pick(v), need, 10 ** 6)
+    assert [split('b', 5), split('b', 9), split('b', 9)] == [5, 5, 5] and calls == [5]
+    site = lambda epi: 1 if (epi & 15) == EPI_GELU else split('c', 5)       # (_g16_fwd, _lin_fwd)
+    assert [site(EPI_NONE), site(EPI_GELU | 16), site(EPI_NONE)] == [5, 1, 5] and cache['c'] == 5
+    assert [1 if (e & 15) == EPI_GELU else split('d', 5) for e in (EPI_GELU, EPI_NONE)] == [1, 5]      # GELU first: nothing cached for it

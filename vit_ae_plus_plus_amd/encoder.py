@@ -24,19 +24,9 @@ from typing import Dict, Tuple
 import torch
 
 from ._abi import CONSTS as _C, VitaeError, lib
+from ._launch import EPI_AUX_BF16, EPI_AUX_DERIV, EPI_DGELU, EPI_GELU, EPI_NONE, PREC, fit_split, pad64 as _pad64, ptr as _ptr
 
-PREC = {'fp32': _C['VITAE_PREC_F32'], 'bf16': _C['VITAE_PREC_BF16'], 'fp32x3': _C['VITAE_PREC_BF16X3']}
-EPI_NONE, EPI_GELU, EPI_DGELU = _C['VITAE_EPI_NONE'], _C['VITAE_EPI_GELU'], _C['VITAE_EPI_DGELU']
-EPI_AUX_BF16, EPI_AUX_DERIV = _C['VITAE_EPI_AUX_BF16'], _C['VITAE_EPI_AUX_DERIV']     # flags, OR-ed into an epilogue above bit 3
 _EMBED = ('cls_token', 'pos_embed', 'patch_embed.proj.weight', 'patch_embed.proj.bias')
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _pad64(M):
-    return (M + 63) // 64 * 64
 
 
 def act16_refusal(precision, embed_dim, hidden, patch_dim, head_dim):
@@ -130,20 +120,11 @@ class HipEncoder:
         b['mean2'], b['rstd2'] = b['mean1'], b['rstd1']
 
     # ------------------------------------------------------------------ launch helpers
-    def _fit_split(self, key, pick, need, capacity):
-        """The split-K of one GEMM shape, cached under ``key``: what the planner ``pick()`` proposes, shrunk until the ``need(s)``
-        floats of scratch it takes fit into ``capacity``.  Call sites look into ``_split`` first, so this runs once per shape."""
-        s = pick()
-        while s > 1 and need(s) > capacity:
-            s -= 1
-        self._split[key] = s
-        return s
-
     def _g16(self, x16, wname, bname, M, N, K, y=None, y16=None, epi=EPI_NONE, aux=None, res=None):
         """y / y16 [M, N] = epi(x16 W16^T + b) (+ res) on the LDS-DMA GEMM; a GELU epilogue cannot be split."""
         ws, key = self.buf['ws16'], ('g', M, N, K, epi)
-        s = self._split.get(key) or self._fit_split(
-            key, lambda: 1 if (epi & 15) == EPI_GELU else lib.vitae_gemm_glds_pick_split_k(M, N, K),
+        s = self._split.get(key) or fit_split(
+            self._split, key, lambda: 1 if (epi & 15) == EPI_GELU else lib.vitae_gemm_glds_pick_split_k(M, N, K),
             lambda s: lib.vitae_gemm_glds_ws_floats(M, N, s), ws.numel())
         lib.vitae_gemm_glds(1, 1, _ptr(x16), K, self._bf16(wname), K, _ptr(y), N, _ptr(y16), N, M, N, K,
                             _ptr(self._param(bname)), _ptr(res), N, epi, _ptr(aux), N, 0, s, ws.data_ptr(), None, self.stream)
@@ -151,8 +132,8 @@ class HipEncoder:
     def _lin(self, x, wname, bname, y, M, N, K, epi=EPI_NONE, aux=None, res=None):
         """y [M, N] = epi(x W^T + b) (+ res) on the generic launcher; any epilogue forces one split."""
         ws, key = self.buf['ws'], ('l', M, N, K, epi)
-        s = self._split.get(key) or self._fit_split(
-            key, lambda: 1 if epi != EPI_NONE else lib.vitae_gemm_pick_split_k(M, N, K), lambda s: s * M * N, ws.numel())
+        s = self._split.get(key) or fit_split(
+            self._split, key, lambda: 1 if epi != EPI_NONE else lib.vitae_gemm_pick_split_k(M, N, K), lambda s: s * M * N, ws.numel())
         lib.vitae_linear_fwd(self.prec, _ptr(x), _ptr(self._param(wname)), _ptr(self._param(bname)), _ptr(y), M, N, K, epi,
                              _ptr(aux), _ptr(res), s, ws.data_ptr(), self.stream)
 
@@ -435,8 +416,8 @@ class HipEncoderTrainer(_Trainer):
     def _split_bwd(self, M, N, K):
         """Split of the reduction (length K) of a backward GEMM with an [M, N] result, fitted to the scratch buffer."""
         key = ('b', M, N, K)
-        return self._split.get(key) or self._fit_split(
-            key, lambda: (lib.vitae_gemm_bf16x3_pick_split_k if self.prec == PREC['fp32x3'] else lib.vitae_gemm_pick_split_k)(M, N, K),
+        return self._split.get(key) or fit_split(
+            self._split, key, lambda: (lib.vitae_gemm_bf16x3_pick_split_k if self.prec == PREC['fp32x3'] else lib.vitae_gemm_pick_split_k)(M, N, K),
             lambda s: s * M * N, self.buf['ws'].numel())
 
     def _lin_bwd(self, grads, needs, dy, wname, bname, x, dx, M, N, K, epi=EPI_NONE, aux=None):
@@ -562,8 +543,8 @@ class HipEncoderTrainer16(_Trainer):
         """Backward of y = x W^T + b on bf16 operands, dy16 [Mpad, N]: dx / dx16 [M, K] = epi(dy16 W16) and, for a trainable weight,
         dW = dy16^T x16 in the same launch.  ``dx_colsum`` / ``dy_colsum`` (zeroed by the caller) collect column sums of dx / dy16."""
         ws, key = self.buf['ws16'], ('p', M, N, K)
-        s = self._split.get(key) or self._fit_split(
-            key, lambda: lib.vitae_linear_bwd_pair_pick_split_k(M, Mpad, N, K), lambda s: lib.vitae_gemm_glds_ws_floats(M, K, s),
+        s = self._split.get(key) or fit_split(
+            self._split, key, lambda: lib.vitae_linear_bwd_pair_pick_split_k(M, Mpad, N, K), lambda s: lib.vitae_gemm_glds_ws_floats(M, K, s),
             ws.numel())
         dw = None
         if needs.get(wname):

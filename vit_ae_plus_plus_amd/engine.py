@@ -22,6 +22,7 @@ from __future__ import annotations
 import os
 
 from collections import OrderedDict
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
@@ -29,12 +30,10 @@ import numpy as np
 import torch
 
 from ._abi import CONSTS, VitaeError, lib
+from ._launch import EPI_DGELU, EPI_GELU, EPI_NONE, EPI_RELU, PREC, fit_split, pad64, ptr as _ptr  # noqa: F401  (EPI_RELU: re-export)
 
 _C = CONSTS
-EPI_NONE, EPI_GELU, EPI_DGELU, EPI_RELU = (_C['VITAE_EPI_NONE'], _C['VITAE_EPI_GELU'], _C['VITAE_EPI_DGELU'],
-                                           _C['VITAE_EPI_RELU_MASK'])
 HP = {k[len('VITAE_HP_'):]: v for k, v in _C.items() if k.startswith('VITAE_HP_')}
-PREC = {'fp32': _C['VITAE_PREC_F32'], 'bf16': _C['VITAE_PREC_BF16'], 'fp32x3': _C['VITAE_PREC_BF16X3']}
 
 
 def _triple(v):
@@ -94,11 +93,22 @@ def gaussian_taps_host(sigma: float = 2.0) -> np.ndarray:
     return (g / g.sum()).astype(np.float32)
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+class _Timed:
+    """The bracket of ``HipMAEEngine._timed``: leaving it records the end event — unless an exception left it, or there is none."""
+    __slots__ = ('end',)
+
+    def __init__(self, end=None):
+        self.end = end
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.end is not None and exc_type is None:
+            self.end.record()
 
 
-_ABLATE_LN_FWD = os.environ.get('VITAE_ABLATE_LN_FWD') == '1'
+_UNTIMED = _Timed()
 
 
 class HipMAEEngine:
@@ -150,6 +160,9 @@ class HipMAEEngine:
         # q | k | v leave the qkv GEMM in bf16 only and the attention kernels read that (no fp32 qkv in HBM: the GEMM epilogue is
         # bound by its output bytes, and the kernels no longer convert while staging); needs the one-launch attention backward
         self.qkv16 = self.act16 and os.environ.get('VITAE_QKV_BF16', '1') != '0'
+        self.qkv16_long = os.environ.get('VITAE_QKV_BF16_LONG', '1') != '0'     # (see _qkv16_ok)
+        self.opt_state16 = os.environ.get('VITAE_OPT_STATE16', '1') != '0'      # (see _state16_ok)
+        self.sq_spread = os.environ.get('VITAE_SQ_SPREAD', '1') != '0'          # (see train_phase)
         self.buffers = buffers   # pos_embed, decoder_pos_embed, BN running stats (device tensors)
         f32 = dict(dtype=torch.float32, device=device)
         # ring of pinned staging buffers: the host may run a few steps ahead of the stream, so the
@@ -488,8 +501,7 @@ class HipMAEEngine:
         if self.act16:
             # bf16 GEMM operands, token rows padded to 64 with zeros (wgrad reduces over the padded count)
             z16 = lambda *s: torch.zeros(*s, dtype=torch.bfloat16, device=dev)
-            pad = lambda m: (m + 63) // 64 * 64
-            self.Mpe, self.Mpd, self.Mpt = pad(Me), pad(Md), pad(Be * keep)
+            self.Mpe, self.Mpd, self.Mpt = pad64(Me), pad64(Md), pad64(Be * keep)
             for pre, depth, Mp, d, h in (('enc', cfg.depth, self.Mpe, D, self.Hm), ('dec', cfg.decoder_depth, self.Mpd, Dd, self.Hmd)):
                 for i in range(depth):
                     q = f'{pre}{i}.'
@@ -508,7 +520,7 @@ class HipMAEEngine:
             # decoder_embed on the LDS-DMA GEMM: its input (the view-1 rows of the latent) and its output gradient in bf16.
             # The wgrad reduces over pad(B * Ne) rows: the pad rows of de_16 stay zero, so whatever finite rows of latent_16
             # (view 2) sit opposite them contribute nothing.
-            self.Mpl = pad(B * Ne)
+            self.Mpl = pad64(B * Ne)
             b['latent_16'], b['de_16'] = z16(max(self.Mpe, self.Mpl), D), z16(self.Mpl, Dd)
             if cfg.contrastive and self.pred16:
                 # predictor on the LDS-DMA GEMMs: bf16 copies of its activations / their gradients (2 R = Me rows, zero pad rows)
@@ -549,27 +561,22 @@ class HipMAEEngine:
         self.mask_sum = float(B * (L - keep))
         self.edge_count = B * V
 
-    # ------------------------------------------------------------------ predictor branch beside the decoder
-    class _OnPredictorStream:
-        """Launch helpers issue on ``pside`` with the branch's own split-K scratch inside this context."""
+    # ------------------------------------------------------------------ branch streams (predictor beside the decoder, grouped wgrads)
+    @contextmanager
+    def _on_branch(self, branch, ws=None, ws16=None):
+        """Launch helpers issue on stream ``branch`` inside this context, with the branch's own split-K scratch in place of
+        whichever of ``ws`` / ``ws16`` is given (tickets / partials are never shared with the chain's)."""
+        saved = (self.stream, self.ws, self.ws16)
+        with torch.cuda.stream(branch):
+            self.stream = branch.cuda_stream
+            self.ws, self.ws16 = ws if ws is not None else self.ws, ws16 if ws16 is not None else self.ws16
+            try:
+                yield
+            finally:
+                self.stream, self.ws, self.ws16 = saved
 
-        def __init__(self, eng):
-            self.eng = eng
-
-        def __enter__(self):
-            e = self.eng
-            self.saved = (e.stream, e.ws, e.ws16)
-            self.ctx = torch.cuda.stream(e.pside)
-            self.ctx.__enter__()
-            e.stream, e.ws = e.pside.cuda_stream, e.ws_side
-            if e.ws16_side is not None:
-                e.ws16 = e.ws16_side        # split-K tickets / partials of the branch's LDS-DMA GEMMs: never shared with the chain's
-            return e
-
-        def __exit__(self, *a):
-            e = self.eng
-            e.stream, e.ws, e.ws16 = self.saved
-            return self.ctx.__exit__(*a)
+    def _on_predictor_stream(self):
+        return self._on_branch(self.pside, ws=self.ws_side, ws16=self.ws16_side)
 
     def _predictor_join(self):
         """Main stream waits for everything issued on the predictor stream."""
@@ -579,15 +586,10 @@ class HipMAEEngine:
 
     # ------------------------------------------------------------------ thin launch helpers
     def _split(self, M, N, K):
+        pick = (lib.vitae_gemm_pick_split_k if self.prec == PREC['fp32'] else lib.vitae_gemm_bf16x3_pick_split_k if self.prec == PREC['fp32x3']
+                else lib.vitae_gemm_bf16_pick_split_k)
         key = (M, N, K)
-        s = self._split_cache.get(key)
-        if s is None:
-            s = (lib.vitae_gemm_pick_split_k if self.prec == PREC['fp32'] else lib.vitae_gemm_bf16x3_pick_split_k if self.prec == PREC['fp32x3']
-                 else lib.vitae_gemm_bf16_pick_split_k)(M, N, K)
-            while s > 1 and s * M * N > self.ws.numel():
-                s -= 1
-            self._split_cache[key] = s
-        return s
+        return self._split_cache.get(key) or fit_split(self._split_cache, key, lambda: pick(M, N, K), lambda s: s * M * N, self.ws.numel())
 
     def _w16(self, w):
         """Device pointer of the bf16 shadow of arena weight ``w`` (0 when ``w`` is not an arena tensor)."""
@@ -598,13 +600,14 @@ class HipMAEEngine:
 
     def _timed(self, flops, tag='other'):
         """bench.py's roofline instrumentation: HIP events around one GEMM launch; ``tag`` names the kernel family
-        ('glds_pair' = gemm_glds_pair_kernel, 'glds' = gemm_glds_kernel, 'other' = gemm_bf16 / fp32 kernels)."""
+        ('glds_pair' = gemm_glds_pair_kernel, 'glds' = gemm_glds_kernel, 'other' = gemm_bf16 / fp32 kernels).  Used as
+        ``with self._timed(flops, tag): <launch>``; untimed, that is one shared no-op bracket."""
         if self.gemm_timer is None:
-            return None
+            return _UNTIMED
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         self.gemm_timer.append((a, b, flops, tag, self._scope))
         a.record()
-        return b
+        return _Timed(b)
 
     def _x3_ok(self, N, K, *ts, M=None) -> bool:
         """vitae_gemm_wsx3 serves this problem (every precondition of its launcher mirrored, so that a tiny batch or token count
@@ -621,35 +624,26 @@ class HipMAEEngine:
 
     def _x3_split(self, M, N, K, ws):
         key = ('x3', M, N, K, ws.numel())
-        s = self._split_cache.get(key)
-        if s is None:
-            s = lib.vitae_gemm_wsx3_pick_split_k(M, N, K)
-            while s > 1 and lib.vitae_gemm_glds_ws_floats(M, N, s) > ws.numel():
-                s -= 1
-            self._split_cache[key] = s
-        return s
+        return self._split_cache.get(key) or fit_split(self._split_cache, key, lambda: lib.vitae_gemm_wsx3_pick_split_k(M, N, K),
+                                                       lambda s: lib.vitae_gemm_glds_ws_floats(M, N, s), ws.numel())
 
     def _lin_fwd(self, x, w, bias, y, M, N, K, epi=EPI_NONE, aux=None, res=None):
         if self._x3_ok(N, K, x, w, y, bias, aux, res, M=M):
             ws = self._x3_ws()
             s = 1 if (epi & 15) == EPI_GELU else self._x3_split(M, N, K, ws)
-            t = self._timed(2.0 * M * N * K)
-            lib.vitae_gemm_wsx3(1, 1, _ptr(x), K, _ptr(w), K, _ptr(y), N, M, N, K, _ptr(bias), _ptr(res), N, epi, _ptr(aux), N, 0, s,
-                                ws.data_ptr(), None, None, self.stream)
-            if t is not None:
-                t.record()
+            with self._timed(2.0 * M * N * K):
+                lib.vitae_gemm_wsx3(1, 1, _ptr(x), K, _ptr(w), K, _ptr(y), N, M, N, K, _ptr(bias), _ptr(res), N, epi, _ptr(aux), N, 0, s,
+                                    ws.data_ptr(), None, None, self.stream)
             return
         s = 1 if (epi & 15) == EPI_GELU else self._split(M, N, K)
-        t = self._timed(2.0 * M * N * K)
-        if self.prec == PREC['bf16']:
-            w16 = self._w16(w)
-            lib.vitae_gemm_bf16(1, 1, _ptr(x), K, w16 if w16 else _ptr(w), K, 1 if w16 else 0, _ptr(y), N, M, N, K,
-                                _ptr(bias), _ptr(res), N, epi, _ptr(aux), N, 0, s, self.ws.data_ptr(), None, self.stream)
-        else:
-            lib.vitae_linear_fwd(self.prec, _ptr(x), _ptr(w), _ptr(bias), _ptr(y), M, N, K, epi, _ptr(aux), _ptr(res), s,
-                                 self.ws.data_ptr(), self.stream)
-        if t is not None:
-            t.record()
+        with self._timed(2.0 * M * N * K):
+            if self.prec == PREC['bf16']:
+                w16 = self._w16(w)
+                lib.vitae_gemm_bf16(1, 1, _ptr(x), K, w16 if w16 else _ptr(w), K, 1 if w16 else 0, _ptr(y), N, M, N, K,
+                                    _ptr(bias), _ptr(res), N, epi, _ptr(aux), N, 0, s, self.ws.data_ptr(), None, self.stream)
+            else:
+                lib.vitae_linear_fwd(self.prec, _ptr(x), _ptr(w), _ptr(bias), _ptr(y), M, N, K, epi, _ptr(aux), _ptr(res), s,
+                                     self.ws.data_ptr(), self.stream)
 
     def _lin_bwd_x(self, dy, w, dx, M, N, K, epi=EPI_NONE, aux=None, accumulate=0, db=None):
         """dx = epi(dy @ W); with ``db`` the bias gradient colsum(dy) rides on the same launch (bf16 mode)
@@ -657,27 +651,23 @@ class HipMAEEngine:
         if self._x3_ok(K, N, dy, w, dx, aux, M=M) and K >= 8:
             ws = self._x3_ws()
             s = self._x3_split(M, K, N, ws)
-            t = self._timed(2.0 * M * N * K)
-            lib.vitae_gemm_wsx3(1, 0, _ptr(dy), N, _ptr(w), K, _ptr(dx), K, M, K, N, None, None, 0, epi, _ptr(aux), K, accumulate, s,
-                                ws.data_ptr(), None, None, self.stream)
-            if db is not None:
-                lib.vitae_colsum_accum(_ptr(dy), N, _ptr(db), M, N, self.stream)
-            if t is not None:
-                t.record()
+            with self._timed(2.0 * M * N * K):
+                lib.vitae_gemm_wsx3(1, 0, _ptr(dy), N, _ptr(w), K, _ptr(dx), K, M, K, N, None, None, 0, epi, _ptr(aux), K, accumulate, s,
+                                    ws.data_ptr(), None, None, self.stream)
+                if db is not None:
+                    lib.vitae_colsum_accum(_ptr(dy), N, _ptr(db), M, N, self.stream)
             return
         s = self._split(M, K, N)
-        t = self._timed(2.0 * M * N * K)
-        if self.prec == PREC['bf16']:
-            w16 = self._w16(w)
-            lib.vitae_gemm_bf16(1, 0, _ptr(dy), N, w16 if w16 else _ptr(w), K, 1 if w16 else 0, _ptr(dx), K, M, K, N,
-                                None, None, 0, epi, _ptr(aux), K, accumulate, s, self.ws.data_ptr(), _ptr(db), self.stream)
-        else:
-            lib.vitae_linear_bwd_input(self.prec, _ptr(dy), _ptr(w), _ptr(dx), M, N, K, epi, _ptr(aux), accumulate, s,
-                                       self.ws.data_ptr(), self.stream)
-            if db is not None:
-                lib.vitae_colsum_accum(_ptr(dy), N, _ptr(db), M, N, self.stream)
-        if t is not None:
-            t.record()
+        with self._timed(2.0 * M * N * K):
+            if self.prec == PREC['bf16']:
+                w16 = self._w16(w)
+                lib.vitae_gemm_bf16(1, 0, _ptr(dy), N, w16 if w16 else _ptr(w), K, 1 if w16 else 0, _ptr(dx), K, M, K, N,
+                                    None, None, 0, epi, _ptr(aux), K, accumulate, s, self.ws.data_ptr(), _ptr(db), self.stream)
+            else:
+                lib.vitae_linear_bwd_input(self.prec, _ptr(dy), _ptr(w), _ptr(dx), M, N, K, epi, _ptr(aux), accumulate, s,
+                                           self.ws.data_ptr(), self.stream)
+                if db is not None:
+                    lib.vitae_colsum_accum(_ptr(dy), N, _ptr(db), M, N, self.stream)
 
     def _lin_bwd_w(self, dy, x, dw, db, M, N, K, tag=None):
         """dW (+)= dy^T x.  With ``tag`` (and overlap enabled) the GEMM is enqueued on the wgrad side stream:
@@ -688,58 +678,49 @@ class HipMAEEngine:
         side = tag is not None and self.overlap_wgrad and self.gemm_timer is None
         ws = self.ws
         if side and s > 1:      # a split reduction beside the chain needs scratch of its own (the chain's GEMMs use self.ws)
-            ws = self.ws_wside
-            while s > 1 and s * N * K > ws.numel():
-                s -= 1
+            ws, s_main, key = self.ws_wside, s, ('wside', N, K, M)
+            s = self._split_cache.get(key) or fit_split(self._split_cache, key, lambda: s_main, lambda s: s * N * K, ws.numel())
         if side:
             main = torch.cuda.current_stream(self.device)
             self.wside.wait_stream(main)
             stream = self.wside.cuda_stream
         else:
             stream = self.stream
-        t = self._timed(2.0 * M * N * K)
-        if self._x3_ok(K, M, dy, x, dw, db, M=N) and N % 4 == 0 and K >= 8:
-            # dW = dy^T x (reduction over the M token rows: any multiple of 4), the bias gradient colsum(dy) by the same launch
-            ws = self._x3_ws(side)       # (split-K tickets: never shared between streams)
-            s3 = self._x3_split(N, K, M, ws)
-            lib.vitae_gemm_wsx3(0, 0, _ptr(dy), N, _ptr(x), K, _ptr(dw), K, N, K, M, None, None, 0, EPI_NONE, None, 0, int(self._accum), s3,
-                                ws.data_ptr(), None, _ptr(db), stream)
-            db = None
-            if self._epi_norm_on:        # this launch added the squares of dW to acc[GRADSQ] (vitae_gemm_glds_set_wgrad_sqnorm)
-                off = (dw.data_ptr() - self.grads.data_ptr()) // 4
-                if 0 <= off < self.tok_off:
-                    # the kernel adds the squares of whatever it stores: a second launch into the same dW inside one grad window
-                    # would count partial + total — every matrix has exactly one weight-gradient launch per step
-                    if any(a < off + N * K and off < e for a, e in self._x3_cov):
-                        raise VitaeError('fp32x3 gradient-norm coverage: two weight-gradient launches into one dW range in one step')
-                    self._x3_cov.append((off, off + N * K))
-        elif self.prec == PREC['bf16']:
-            lib.vitae_gemm_bf16(0, 0, _ptr(dy), N, _ptr(x), K, 0, _ptr(dw), K, N, K, M, None, None, 0, EPI_NONE, None, 0,
-                                int(self._accum), s, ws.data_ptr(), None, stream)
-        else:
-            lib.vitae_linear_bwd_weight(self.prec, _ptr(dy), _ptr(x), _ptr(dw), M, N, K, int(self._accum), s,
-                                        ws.data_ptr(), stream)
-        if t is not None:
-            t.record()
+        with self._timed(2.0 * M * N * K):
+            if self._x3_ok(K, M, dy, x, dw, db, M=N) and N % 4 == 0 and K >= 8:
+                # dW = dy^T x (reduction over the M token rows: any multiple of 4), the bias gradient colsum(dy) by the same launch
+                ws = self._x3_ws(side)       # (split-K tickets: never shared between streams)
+                s3 = self._x3_split(N, K, M, ws)
+                lib.vitae_gemm_wsx3(0, 0, _ptr(dy), N, _ptr(x), K, _ptr(dw), K, N, K, M, None, None, 0, EPI_NONE, None, 0, int(self._accum),
+                                    s3, ws.data_ptr(), None, _ptr(db), stream)
+                db = None
+                if self._epi_norm_on:        # this launch added the squares of dW to acc[GRADSQ] (vitae_gemm_glds_set_wgrad_sqnorm)
+                    off = (dw.data_ptr() - self.grads.data_ptr()) // 4
+                    if 0 <= off < self.tok_off:
+                        # the kernel adds the squares of whatever it stores: a second launch into the same dW inside one grad window
+                        # would count partial + total — every matrix has exactly one weight-gradient launch per step
+                        if any(a < off + N * K and off < e for a, e in self._x3_cov):
+                            raise VitaeError('fp32x3 gradient-norm coverage: two weight-gradient launches into one dW range in one step')
+                        self._x3_cov.append((off, off + N * K))
+            elif self.prec == PREC['bf16']:
+                lib.vitae_gemm_bf16(0, 0, _ptr(dy), N, _ptr(x), K, 0, _ptr(dw), K, N, K, M, None, None, 0, EPI_NONE, None, 0,
+                                    int(self._accum), s, ws.data_ptr(), None, stream)
+            else:
+                lib.vitae_linear_bwd_weight(self.prec, _ptr(dy), _ptr(x), _ptr(dw), M, N, K, int(self._accum), s,
+                                            ws.data_ptr(), stream)
         if db is not None:
             lib.vitae_colsum_accum(_ptr(dy), N, _ptr(db), M, N, stream)
         if side:
-            ev = self._wg_events.get(tag)
-            if ev is None:
-                ev = self._wg_events[tag] = torch.cuda.Event()
-            ev.record(self.wside)
-            self._wg_pending.add(tag)
+            self._wg_mark(tag)
 
     def _lin_bwd(self, dy, w, x, dx, dw, db, M, N, K, epi=EPI_NONE, aux=None, dx_accumulate=0, tag=None):
         """Full backward of y = x W^T + b given dy: dx (+)= epi(dy W), dW (+)= dy^T x, db += colsum(dy).
         bf16 mode: ONE paired launch (dgrad + wgrad blocks side by side); fp32 mode: separate launches."""
         w16 = self._w16(w) if self.prec == PREC['bf16'] else 0
         if w16:
-            t = self._timed(4.0 * M * N * K)   # dgrad + wgrad
-            lib.vitae_linear_bwd_pair_bf16(_ptr(dy), w16, _ptr(x), _ptr(dx), _ptr(dw), _ptr(db), M, N, K, epi, _ptr(aux),
-                                           dx_accumulate, int(self._accum), self.stream)
-            if t is not None:
-                t.record()
+            with self._timed(4.0 * M * N * K):   # dgrad + wgrad
+                lib.vitae_linear_bwd_pair_bf16(_ptr(dy), w16, _ptr(x), _ptr(dx), _ptr(dw), _ptr(db), M, N, K, epi, _ptr(aux),
+                                               dx_accumulate, int(self._accum), self.stream)
             return
         # the bias gradient colsum(dy) goes with the weight gradient (both only read dy; on the wgrad side stream when that overlaps):
         # as a separate launch on the main chain it was 84 x 11 us = 0.9 ms of the fp32-mode step
@@ -755,6 +736,10 @@ class HipMAEEngine:
             return
         self.wside.wait_stream(torch.cuda.current_stream(self.device))
         lib.vitae_colsum_accum(_ptr(x), ld, _ptr(out), M, N, self.wside.cuda_stream)
+        self._wg_mark(tag)
+
+    def _wg_mark(self, tag):
+        """What was just issued on the wgrad side stream reads buffer ``tag``: record the tag's event there and mark it pending."""
         ev = self._wg_events.get(tag)
         if ev is None:
             ev = self._wg_events[tag] = torch.cuda.Event()
@@ -774,8 +759,6 @@ class HipMAEEngine:
             self._wg_pending.clear()
 
     def _ln_fwd(self, x, pre, y, mean, rstd, M, D, y16=None):
-        if _ABLATE_LN_FWD and pre.startswith(('blocks.', 'decoder_blocks.')):   # timing ablation only (results are garbage)
-            return
         lib.vitae_layernorm_fwd(_ptr(x), _ptr(self.p[pre + 'weight']), _ptr(self.p[pre + 'bias']), _ptr(y), _ptr(y16),
                                 _ptr(mean), _ptr(rstd), M, D, self.cfg.ln_eps, self.stream)
 
@@ -816,36 +799,26 @@ class HipMAEEngine:
     # ------------------------------------------------------------------ bf16-activation GEMM helpers (LDS-DMA kernel)
     def _g16_fwd(self, x16, w, bias, M, N, K, y=None, y16=None, epi=EPI_NONE, aux=None, res=None, name=None):
         """y / y16 = epi(x16 @ W16^T + b) (+ res) on the LDS-DMA GEMM (bf16 operands in HBM)."""
-        key = ('g', M, N, K, self.ws16.numel())
-        s = self._split_cache.get(key)
-        if s is None:
-            s = 1 if (epi & 15) == EPI_GELU else lib.vitae_gemm_glds_pick_split_k(M, N, K)
-            while s > 1 and lib.vitae_gemm_glds_ws_floats(M, N, s) > self.ws16.numel():
-                s -= 1
-            self._split_cache[key] = s
+        gelu, cap = (epi & 15) == EPI_GELU, self.ws16.numel()      # (a GELU epilogue is never split: decided outside the cache)
+        need = lambda s: lib.vitae_gemm_glds_ws_floats(M, N, s)
+        key = ('g', M, N, K, cap)
+        s = 1 if gelu else self._split_cache.get(key) or fit_split(self._split_cache, key, lambda: lib.vitae_gemm_glds_pick_split_k(M, N, K),
+                                                                   need, cap)
         w2 = self._w2.get(name) if name is not None else None
         if w2 is not None:
             # two-plane weight ([W hi | W lo] side by side): the two-plane 64 x 64 workgroup, or a big tile over 2 K with x16 wrapping
-            key2 = ('w2', M, N, K, self.ws16.numel())
-            s2 = self._split_cache.get(key2)
-            if s2 is None:
-                s2 = 1 if (epi & 15) == EPI_GELU else lib.vitae_gemm_glds_w2_pick_split_k(M, N, K)
-                while s2 > 1 and lib.vitae_gemm_glds_ws_floats(M, N, s2) > self.ws16.numel():
-                    s2 -= 1
-                self._split_cache[key2] = s2
+            key = ('w2', M, N, K, cap)
+            s2 = 1 if gelu else self._split_cache.get(key) or fit_split(
+                self._split_cache, key, lambda: lib.vitae_gemm_glds_w2_pick_split_k(M, N, K), need, cap)
             # (algorithmic FLOPs: the second plane's MFMAs are not counted as work; the tag follows the planner of the two-plane form:
             # the 64 x 64 two-plane workgroup, or a big tile over 2 K)
-            t = self._timed(2.0 * M * N * K, self._w2_tag(M, N, K))
-            lib.vitae_gemm_glds_w2(_ptr(x16), K, _ptr(w2), _ptr(y), N, _ptr(y16), N, M, N, K, _ptr(bias), _ptr(res), N,
-                                   epi, _ptr(aux), N, 0, s2, self.ws16.data_ptr(), None, self.stream)
-            if t is not None:
-                t.record()
+            with self._timed(2.0 * M * N * K, self._w2_tag(M, N, K)):
+                lib.vitae_gemm_glds_w2(_ptr(x16), K, _ptr(w2), _ptr(y), N, _ptr(y16), N, M, N, K, _ptr(bias), _ptr(res), N,
+                                       epi, _ptr(aux), N, 0, s2, self.ws16.data_ptr(), None, self.stream)
             return
-        t = self._timed(2.0 * M * N * K, self._gemm_tag(1, 1, M, N, K, s, 'glds' if N < 8192 else 'glds_wide'))   # wide = the 64x128-tile instantiation
-        lib.vitae_gemm_glds(1, 1, _ptr(x16), K, self._w16(w), K, _ptr(y), N, _ptr(y16), N, M, N, K, _ptr(bias), _ptr(res), N,
-                            epi, _ptr(aux), N, 0, s, self.ws16.data_ptr(), None, self.stream)
-        if t is not None:
-            t.record()
+        with self._timed(2.0 * M * N * K, self._gemm_tag(1, 1, M, N, K, s, 'glds' if N < 8192 else 'glds_wide')):   # wide = the 64x128-tile instantiation
+            lib.vitae_gemm_glds(1, 1, _ptr(x16), K, self._w16(w), K, _ptr(y), N, _ptr(y16), N, M, N, K, _ptr(bias), _ptr(res), N,
+                                epi, _ptr(aux), N, 0, s, self.ws16.data_ptr(), None, self.stream)
 
     def _w2_tag(self, M, N, K):
         if self.gemm_timer is None:
@@ -909,12 +882,8 @@ class HipMAEEngine:
         """dx / dx16 = epi(dy16 @ W16), dW (+)= dy16^T @ x16 in one paired launch.  ``dw`` None: the input gradient only (the
         weight gradient is collected by ``_wgrad_group``)."""
         key = ('p', M, N, K, self.ws16.numel())
-        s = self._split_cache.get(key)
-        if s is None:
-            s = lib.vitae_linear_bwd_pair_pick_split_k(M, Mpad, N, K)
-            while s > 1 and lib.vitae_gemm_glds_ws_floats(M, K, s) > self.ws16.numel():
-                s -= 1
-            self._split_cache[key] = s
+        s = self._split_cache.get(key) or fit_split(self._split_cache, key, lambda: lib.vitae_linear_bwd_pair_pick_split_k(M, Mpad, N, K),
+                                                    lambda s: lib.vitae_gemm_glds_ws_floats(M, K, s), self.ws16.numel())
         tag = 'glds_pair' if N < 8192 else 'glds_pair_wide'
         if self.gemm_timer is not None:
             cd, cw = lib.vitae_gemm_glds_bt_choice(1, 0, M, K, N), lib.vitae_gemm_glds_bt_choice(0, 0, N, K, Mpad)
@@ -924,15 +893,11 @@ class HipMAEEngine:
                 tag = 'bt_bwd'      # the halves leave as two launches, at least one of them on a big tile
         if dw is None:
             tag = self._gemm_tag(1, 0, M, K, N, lib.vitae_gemm_glds_pick_split_k(M, K, N), 'glds')
-        t = self._timed((4.0 if dw is not None else 2.0) * M * N * K, tag)
-        lib.vitae_linear_bwd_pair_glds(_ptr(dy16), self._w16(w), _ptr(x16), _ptr(dx), _ptr(dx16), _ptr(dw),
-                                       None if dw is None else self._wire_of(dw), M, Mpad,
-                                       N, K,
-                                       epi, _ptr(aux), _ptr(dx_colsum), _ptr(dy_colsum), int(dx_accumulate), int(self._accum), s,
-                                       self.ws16.data_ptr(), self.ws16.numel(),
-                                       self.stream)
-        if t is not None:
-            t.record()
+        with self._timed((4.0 if dw is not None else 2.0) * M * N * K, tag):
+            lib.vitae_linear_bwd_pair_glds(_ptr(dy16), self._w16(w), _ptr(x16), _ptr(dx), _ptr(dx16), _ptr(dw),
+                                           None if dw is None else self._wire_of(dw), M, Mpad, N, K,
+                                           epi, _ptr(aux), _ptr(dx_colsum), _ptr(dy_colsum), int(dx_accumulate), int(self._accum), s,
+                                           self.ws16.data_ptr(), self.ws16.numel(), self.stream)
 
     def _wgrad_group(self, items, M, Mpad, bias=None):
         """The weight gradients of one block's Linears in ONE launch (csrc/gemm_bt.hip: gemm_bt_wgrad_group_kernel).
@@ -945,12 +910,10 @@ class HipMAEEngine:
         a_16 = arr([w or 0 for w in wires]) if any(wires) else None
         a_db = arr([(bias[i].data_ptr() if bias and i in bias else 0) for i in range(n)]) if bias else None
         Ns, Ks = np.array([it[3] for it in items], dtype=np.int32), np.array([it[4] for it in items], dtype=np.int32)
-        t = self._timed(sum(2.0 * Mpad * it[3] * it[4] for it in items), 'bt_group')
-        lib.vitae_wgrad_group_bt(n, a_dy.ctypes.data, a_x.ctypes.data, a_dw.ctypes.data, None if a_16 is None else a_16.ctypes.data,
-                                 None if a_db is None else a_db.ctypes.data, Ns.ctypes.data, Ks.ctypes.data, M, Mpad, int(self._accum),
-                                 self.ws16.data_ptr(), self.ws16.numel(), self.stream)
-        if t is not None:
-            t.record()
+        with self._timed(sum(2.0 * Mpad * it[3] * it[4] for it in items), 'bt_group'):
+            lib.vitae_wgrad_group_bt(n, a_dy.ctypes.data, a_x.ctypes.data, a_dw.ctypes.data, None if a_16 is None else a_16.ctypes.data,
+                                     None if a_db is None else a_db.ctypes.data, Ns.ctypes.data, Ks.ctypes.data, M, Mpad, int(self._accum),
+                                     self.ws16.data_ptr(), self.ws16.numel(), self.stream)
 
     # ------------------------------------------------------------------ transformer block
     def _block_fwd16(self, pre, q, x_in, x_out, Bs, N, d, heads, hd, hid):
@@ -961,15 +924,13 @@ class HipMAEEngine:
         self._ln_fwd(x_in, pre + 'norm1.', None, b[q + 'mean1'], b[q + 'rstd1'], M, d, y16=b[q + 'y1_16'])
         self._g16_fwd(b[q + 'y1_16'], p[pre + 'attn.qkv.weight'], p[pre + 'attn.qkv.bias'], M, 3 * d, d, y=qkv32, y16=qkv16,
                       name=pre + 'attn.qkv.weight')
-        t = self._timed(4.0 * Bs * heads * N * N * hd, 'attn')
-        if q16:
-            lib.vitae_sdpa_mfma_fwd_bf16in(_ptr(qkv16), _ptr(b[q + 'o']), _ptr(b[q + 'o_16']), _ptr(b[q + 'lse']), Bs, N, heads, hd,
-                                           self.stream)
-        else:
-            lib.vitae_sdpa_mfma_fwd(_ptr(b[q + 'qkv']), _ptr(b[q + 'o']), _ptr(b[q + 'o_16']), _ptr(b[q + 'lse']), Bs, N, heads, hd,
-                                    self.stream)
-        if t is not None:
-            t.record()
+        with self._timed(4.0 * Bs * heads * N * N * hd, 'attn'):
+            if q16:
+                lib.vitae_sdpa_mfma_fwd_bf16in(_ptr(qkv16), _ptr(b[q + 'o']), _ptr(b[q + 'o_16']), _ptr(b[q + 'lse']), Bs, N, heads, hd,
+                                               self.stream)
+            else:
+                lib.vitae_sdpa_mfma_fwd(_ptr(b[q + 'qkv']), _ptr(b[q + 'o']), _ptr(b[q + 'o_16']), _ptr(b[q + 'lse']), Bs, N, heads, hd,
+                                        self.stream)
         self._g16_fwd(b[q + 'o_16'], p[pre + 'attn.proj.weight'], p[pre + 'attn.proj.bias'], M, d, d, y=b[q + 'xmid'], res=x_in,
                       name=pre + 'attn.proj.weight')
         self._ln_fwd(b[q + 'xmid'], pre + 'norm2.', None, b[q + 'mean2'], b[q + 'rstd2'], M, d, y16=b[q + 'y2_16'])
@@ -983,14 +944,12 @@ class HipMAEEngine:
         kernels read the bf16 copy as well; VITAE_QKV_BF16_LONG=0 keeps fp32 q | k | v when the head does not fit LDS)"""
         if not (self.qkv16 and hd in (32, 64)):
             return False
-        return bool(lib.vitae_sdpa_bwd_fused_fits(N, hd) or os.environ.get('VITAE_QKV_BF16_LONG', '1') != '0')
+        return bool(lib.vitae_sdpa_bwd_fused_fits(N, hd) or self.qkv16_long)
 
     def _dqkv32(self, dqkv, N, hd):
         """fp32 dqkv is write-only on the bf16-operand path (the qkv weight / input gradients read the bf16 copy): skip it
-        whenever the one-launch attention backward applies (its LDS budget: whole head resident)."""
-        NP = (N + 31) // 32 * 32
-        lds = 4 * NP * (hd + 8) * 2 + 2 * NP * 4 + 3 * hd * 4
-        return None if (lds <= 150 * 1024 and os.environ.get('VITAE_ATTN_BWD_FUSED', '1') != '0') else dqkv
+        whenever the one-launch attention backward applies (whole head resident in LDS: csrc/attention_mfma.hip answers)."""
+        return None if lib.vitae_sdpa_bwd_fused_fits(N, hd) else dqkv
 
     def _dyset(self, i, Mp, d) -> str:
         """Suffix of the buffer set that holds block i's output-gradient operands (side-stream grouped weight gradients: two
@@ -1029,20 +988,17 @@ class HipMAEEngine:
         self._ln_bwd(dy, b[q + 'xmid'], pre + 'norm2.', b[q + 'mean2'], b[q + 'rstd2'], dx, M, d, 1, dx16=dmid16,
                      dx_colsum=g[pre + 'attn.proj.bias'])
         self._g16_bwd(dmid16, p[pre + 'attn.proj.weight'], b[q + 'o_16'], dw(pre + 'attn.proj.weight'), M, Mp, d, d, dx=do)
-        t = self._timed(10.0 * Bs * heads * N * N * hd, 'attn')
         # grouped weight gradients: the qkv bias gradient colsum(dqkv) is collected by the attention backward itself (wave
         # shuffles + one atomic per column and workgroup) — as a separate bf16 column-sum launch it was 9-10 us on the main chain of
         # each of the 20 blocks at batch 32 / patch 8
         qkv_db = g[pre + 'attn.qkv.bias'] if (grp and self.attn_bias_colsum) else None
-        if self._qkv16_ok(N, hd):
-            lib.vitae_sdpa_mfma_bwd_bf16in(_ptr(b[q + 'qkv_16']), _ptr(b[q + 'o']), _ptr(do), _ptr(b[q + 'lse']), None, _ptr(dqkv16),
-                                           _ptr(qkv_db), _ptr(b['delta']),
-                                           Bs, N, heads, hd, self.stream)
-        else:
-            lib.vitae_sdpa_mfma_bwd(_ptr(b[q + 'qkv']), _ptr(b[q + 'o']), _ptr(do), _ptr(b[q + 'lse']), _ptr(self._dqkv32(dqkv, N, hd)),
-                                    _ptr(dqkv16), None, _ptr(b['delta']), Bs, N, heads, hd, self.stream)
-        if t is not None:
-            t.record()
+        with self._timed(10.0 * Bs * heads * N * N * hd, 'attn'):
+            if self._qkv16_ok(N, hd):
+                lib.vitae_sdpa_mfma_bwd_bf16in(_ptr(b[q + 'qkv_16']), _ptr(b[q + 'o']), _ptr(do), _ptr(b[q + 'lse']), None, _ptr(dqkv16),
+                                               _ptr(qkv_db), _ptr(b['delta']), Bs, N, heads, hd, self.stream)
+            else:
+                lib.vitae_sdpa_mfma_bwd(_ptr(b[q + 'qkv']), _ptr(b[q + 'o']), _ptr(do), _ptr(b[q + 'lse']), _ptr(self._dqkv32(dqkv, N, hd)),
+                                        _ptr(dqkv16), None, _ptr(b['delta']), Bs, N, heads, hd, self.stream)
         # the qkv bias gradient colsum(dqkv) rides on the wgrad workgroups (one extra MFMA against a ones operand)
         self._g16_bwd(dqkv16, p[pre + 'attn.qkv.weight'], b[q + 'y1_16'], dw(pre + 'attn.qkv.weight'), M, Mp, 3 * d, d, dx=dy,
                       dy_colsum=None if grp else g[pre + 'attn.qkv.bias'])
@@ -1054,20 +1010,10 @@ class HipMAEEngine:
             bias = None if (qkv_db is not None and self._qkv16_ok(N, hd)) else {3: g[pre + 'attn.qkv.bias']}
             if side:
                 # beside the chain: its launches leave a third of the CUs idle, and nothing reads these gradients before the phase ends
-                tag = f'{s}grp{idx & 1}'
                 self.wside.wait_stream(torch.cuda.current_stream(self.device))
-                saved = (self.stream, self.ws16)
-                self.stream, self.ws16 = self.wside.cuda_stream, self.ws16_wside
-                try:
-                    with torch.cuda.stream(self.wside):
-                        self._wgrad_group(items, M, Mp, bias=bias)
-                finally:
-                    self.stream, self.ws16 = saved
-                ev = self._wg_events.get(tag)
-                if ev is None:
-                    ev = self._wg_events[tag] = torch.cuda.Event()
-                ev.record(self.wside)
-                self._wg_pending.add(tag)
+                with self._on_branch(self.wside, ws16=self.ws16_wside):
+                    self._wgrad_group(items, M, Mp, bias=bias)
+                self._wg_mark(f'{s}grp{idx & 1}')
                 self._wg_fence(f'{s}grp{(idx + 1) & 1}')    # norm1 writes the OTHER set's dx16, which block idx + 1's launch reads
             else:
                 self._wgrad_group(items, M, Mp, bias=bias)
@@ -1217,7 +1163,7 @@ class HipMAEEngine:
         if cfg.contrastive and self.overlap_predictor:
             # the predictor branch only needs the latent: it runs on its own stream beside the decoder and the loss chain
             self.pside.wait_stream(torch.cuda.current_stream(self.device))
-            with self._OnPredictorStream(self):
+            with self._on_predictor_stream():
                 self._predictor_fwd(training, None)
             self._pred_pending = True
         if fork == 'decoder':
@@ -1313,7 +1259,7 @@ class HipMAEEngine:
         if self._pred_pending:
             # the branch's backward accumulates into gradient slots zeroed by begin_grad_window on the main stream
             self.pside.wait_stream(torch.cuda.current_stream(self.device))
-            with self._OnPredictorStream(self):
+            with self._on_predictor_stream():
                 self._cosine_bwd(p1, z2, p2, z1, o)
                 self._predictor_bwd()
             return
@@ -1516,12 +1462,10 @@ class HipMAEEngine:
         if self.act16:
             self._colsum_beside(b['dtok'], D, g['patch_embed.proj.bias'], T, D, 'dtok')     # beside the wgrad below
             # dW[D, P] = dtok16^T @ patches16 (both row-contiguous bf16, reduced over the padded token count)
-            t = self._timed(2.0 * T * D * P, 'glds_wide')
-            lib.vitae_gemm_glds(0, 0, _ptr(b['dtok_16']), D, _ptr(b['patches_16']), P, _ptr(g['patch_embed.proj.weight']), P,
-                                self._wire_of(g['patch_embed.proj.weight']), P, D, P, self.Mpt, None, None, 0, EPI_NONE, None, 0,
-                                int(self._accum), 1, None, None, self.stream)
-            if t is not None:
-                t.record()
+            with self._timed(2.0 * T * D * P, 'glds_wide'):
+                lib.vitae_gemm_glds(0, 0, _ptr(b['dtok_16']), D, _ptr(b['patches_16']), P, _ptr(g['patch_embed.proj.weight']), P,
+                                    self._wire_of(g['patch_embed.proj.weight']), P, D, P, self.Mpt, None, None, 0, EPI_NONE, None, 0,
+                                    int(self._accum), 1, None, None, self.stream)
         else:
             self._lin_bwd_w(b['dtok'], b['patches'], g['patch_embed.proj.weight'], g['patch_embed.proj.bias'], T, D, P)
         self._ln_flush(final=True)
@@ -1537,7 +1481,7 @@ class HipMAEEngine:
     _STATE16_MAX_BETA = 1.0 - 2.0 ** -6
 
     def _state16_ok(self, betas) -> bool:
-        return (self.prec == PREC['bf16'] and os.environ.get('VITAE_OPT_STATE16', '1') != '0'
+        return (self.prec == PREC['bf16'] and self.opt_state16
                 and max(float(betas[0]), float(betas[1])) <= self._STATE16_MAX_BETA)
 
     def init_optimizer(self, weight_decay: float = 0.05, betas=(0.9, 0.95), eps: float = 1e-8):
@@ -1786,7 +1730,7 @@ class HipMAEEngine:
         cfg = self.cfg
         n, nd = self.enc_chunks, self.dec_chunks
         self._epi_norm_on = bool(self.epi_norm and update and self._optimizer_in_backward_ok())
-        if self._epi_norm_on and os.environ.get('VITAE_SQ_SPREAD', '1') == '0':      # (A/B knob: everything on acc[GRADSQ], the form up to round 5)
+        if self._epi_norm_on and not self.sq_spread:      # (A/B knob: everything on acc[GRADSQ], the form up to round 5)
             lib.vitae_gemm_glds_set_wgrad_sqnorm(self.acc.data_ptr() + 8 * _C['VITAE_ACC_GRADSQ'])
         elif self._epi_norm_on:    # (spread slots: same-address double atomics retire one per ~10 ns — 576 of them per weight-gradient launch)
             lib.vitae_gemm_glds_set_wgrad_sqnorm_spread(self.acc.data_ptr() + 8 * _C['VITAE_ACC_SQ_BASE'], _C['VITAE_ACC_SQ_SLOTS'],
