@@ -1,5 +1,5 @@
 """Where a wave-specialised 64 x 64 launch spends its time (round 6): s_memtime stamps of consumer wave 0 and producer wave 4 of
-EVERY workgroup of one launch (csrc/gemm_bt.hip: gemm_ws64_body's `stamp`), for the paired backward launches of the batch-4 step
+EVERY workgroup of one launch (csrc/gemm_ws64.hip: gemm_ws64_body's `stamp`), for the paired backward launches of the batch-4 step
 and their halves alone.
     python tools/ws64_phase_probe.py [B=4]
 Per launch: when workgroups start (dispatch ramp), how long each phase takes (median over workgroups, shader clocks), when the

@@ -1,4 +1,4 @@
-"""Who waits for whom in the wave-specialised 128 x 128 k-loop (csrc/gemm_bt.hip: gemm_ws_body): s_memtime stamps of consumer wave 0
+"""Who waits for whom in the wave-specialised 128 x 128 k-loop (csrc/gemm_ws.hip: gemm_ws_body): s_memtime stamps of consumer wave 0
 and producer wave 4 of every workgroup around the barriers B_4 .. B_9 (arrival = the wave has done its part of the k-tile,
 departure = the barrier released it).  python tools/ws_phase_probe.py [M N K [form]]"""
 import os, sys

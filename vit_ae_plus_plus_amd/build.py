@@ -17,7 +17,8 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, 'csrc')
 OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(PKG, 'libvitae_hip.so')
-SOURCES = ['gemm.hip', 'gemm_bf16.hip', 'gemm_glds.hip', 'gemm_bt.hip', 'norm.hip', 'attention.hip', 'attention_mfma.hip', 'tokens.hip', 'vit_train.hip', 'classify.hip', 'loss.hip', 'loss_fused.hip',
+# (the longest compiles first, so that the four workers start them together: gemm_ws ~70 s, gemm_bt ~45 s, gemm_glds and gemm_ws64 ~30 s)
+SOURCES = ['gemm_ws.hip', 'gemm_bt.hip', 'gemm_glds.hip', 'gemm_ws64.hip', 'gemm_ws64q.hip', 'gemm_wsx3.hip', 'gemm.hip', 'gemm_bf16.hip', 'norm.hip', 'attention.hip', 'attention_mfma.hip', 'tokens.hip', 'vit_train.hip', 'classify.hip', 'loss.hip', 'loss_fused.hip',
            'optim.hip', 'moco.hip', 'input.hip', 'blur.hip', 'ddp.hip', 'percep.hip', 'conv3d.hip']
 # -amdgpu-kernarg-preload-count=16: the first 16 dwords of a kernel's scalar / pointer arguments arrive in SGPRs with the dispatch instead
 # of through a cold scalar load at the top of every launch (round 6: the batch-4 step 3.662 -> 3.636 ms, alternating A/B; kernels that take
@@ -52,7 +53,8 @@ def _newer(a: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'glds_tiles.hpp'), os.path.join(CSRC, 'glds_gemm.hpp'), os.path.join(ROOT, 'include', 'vitae_hip.h')]
+    # every header of the tree: a source is rebuilt when any of them is newer than its object (nobody has to keep a list in step)
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hpp')) + [os.path.join(ROOT, 'include', 'vitae_hip.h')]
     hipcc = _hipcc()
     objs, jobs = [], []
     for s in SOURCES:

@@ -150,17 +150,14 @@ __device__ __forceinline__ void epilogue_rows(const GArgs& p, const float (&a)[N
 #pragma unroll
                 for (int e = 0; e < 4; ++e) x[e] += rs[q][e];
             }
-#ifndef VITAE_EPI_ABLATE
-#define VITAE_EPI_ABLATE 0       // timing ablations of the row-major epilogue: 1 = no global stores, 2 = fp32 store only
-#endif
             if (p.C) {
                 if (acc_c) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) x[e] += co[q][e];
                 }
-                if (VITAE_EPI_ABLATE != 1) *reinterpret_cast<f32x4*>(p.C + m * ldc + n) = x;
+                *reinterpret_cast<f32x4*>(p.C + m * ldc + n) = x;
             }
-            if (p.C16 && VITAE_EPI_ABLATE == 0) {
+            if (p.C16) {
                 bf16x4 x16;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) x16[e] = (__bf16)x[e];
@@ -829,7 +826,7 @@ extern "C" int vitae_gemm_glds(int a_kcontig, int b_kcontig, const void* A16, lo
 }
 
 // plan of the two-plane launch: the big tiles see an ordinary forward problem with a reduction of 2 K; tile 5 / no big tile: the
-// two-plane workgroup of gemm_bt.hip (ws64_w2_launch) on the K-deep reduction
+// two-plane workgroup of gemm_ws64.hip (ws64_w2_launch) on the K-deep reduction
 static BtPlan w2_plan(int M, int N, int K, bool allow_split) {
     BtPlan bp = bt_plan(M, N, 2 * K, 1, 1, allow_split);
     if (bp.tile == 5 || bp.tile < 0) {
@@ -878,7 +875,7 @@ extern "C" int vitae_gemm_glds_w2(const void* A16, long lda, const void* B16_hil
     return ws64_w2_launch(p, (hipStream_t)stream);
 }
 
-// fp32x3 on the wave-specialised 64 x 64 workgroup (csrc/gemm_bt.hip: gemm_wsx3_kernel): the contract of vitae_gemm with fp32
+// fp32x3 on the wave-specialised 64 x 64 workgroup (csrc/gemm_wsx3.hip: gemm_wsx3_kernel): the contract of vitae_gemm with fp32
 // operands multiplied as bf16 hi + lo pairs; the producer waves split them while they stage.  K any multiple of 4; in-launch
 // split-K with the workspace layout of vitae_gemm_glds (vitae_gemm_glds_ws_floats(M, N, split_k) floats, first VITAE_GLDS_TICKETS
 // words zero before the first use).  a_rowsum_accum (weight-gradient form, a_kcontig = b_kcontig = 0): [M] += sum_k A(m, k), the
@@ -969,7 +966,7 @@ extern "C" int vitae_linear_bwd_pair_glds(const void* dy16, const void* w16, con
         return gemm_glds_launch(1, 0, dy16, N, w16, K, dx, K, dx16, K, M, K, N, nullptr, nullptr, 0, epi | epi_flags,
                                 aux, K, dx_accumulate, sp, splitk_ws, dx_colsum_accum, stream, &pd);
     }
-    // both halves as wave-specialised 64 x 64 workgroups of ONE launch (gemm_bt.hip: gemm_ws64_pair_kernel), the input gradient cut `split` ways
+    // both halves as wave-specialised 64 x 64 workgroups of ONE launch (gemm_ws64.hip: gemm_ws64_pair_kernel), the input gradient cut `split` ways
     auto ws64_pair = [&](int split) -> int {
         GArgs p1, p2;
         p1.A = reinterpret_cast<const __bf16*>(dy16); p1.lda = N;
@@ -990,7 +987,7 @@ extern "C" int vitae_linear_bwd_pair_glds(const void* dy16, const void* w16, con
         p2.xcd_m = xcd_by_rows(N, K); p2.tiles_m = 0; p2.tiles_n = 0;
         p2.vec_epi = vec_epilogue_ok(p2);
         if (!p1.vec_epi || !p2.vec_epi) return VITAE_ERR_UNSUPPORTED_SHAPE;
-        // VITAE_WS64Q=1: the persistent form (round 6: csrc/gemm_bt.hip gemm_ws64q_pair_kernel — correct, measured 6-10 % SLOWER than
+        // VITAE_WS64Q=1: the persistent form (round 6: csrc/gemm_ws64q.hip gemm_ws64q_pair_kernel — correct, measured 6-10 % SLOWER than
         // one tile per workgroup on the batch-4 / batch-8 pair launches, so it is opt-in; read per call so that a test can switch it)
         const char* wsq_env = getenv("VITAE_WS64Q");
         const int wsq = wsq_env ? atoi(wsq_env) : 0;
@@ -1114,7 +1111,7 @@ extern "C" int vitae_wgrad_group_bt(int n, const void* const* dy16, const void* 
         tiles += (long)p.tiles_m * p.tiles_n;
         tiles2 += (long)cdiv(N[i], 128) * cdiv(K[i], 256);
     }
-    // Two workgroup kinds (csrc/gemm_bt.hip), each with its own split of the reduction; the cheaper by the clocks fitted to
+    // Two workgroup kinds (csrc/gemm_bt.hip, csrc/gemm_ws.hip), each with its own split of the reduction; the cheaper by the clocks fitted to
     // tools/wgrad_group_bench.py wins:
     //   ping-pong 128 x 128, two per CU: 12000 + 2650 per k-tile (both co-resident workgroups advance one) + the split fix-up
     //     (batch 32: encoder block, 432 tiles x 55 k-tiles unsplit, 66 us; decoder block, 192 x 109 at split 2, 73 us);

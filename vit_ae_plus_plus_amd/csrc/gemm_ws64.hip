@@ -1,0 +1,282 @@
+// The wave-specialised structure of gemm_ws.hip (four MFMA waves, producer waves that only issue LDS-DMA, one workgroup barrier per
+// k-tile) on a 64 x 64 tile (tile id 5): the few-row launches of the batch-4 / batch-8 step.  Stand-alone, with a two-plane weight
+// operand, and as the paired dgrad + wgrad launch of one Linear's backward.
+// At 440-1736 token rows a launch is 84-700 workgroups of a handful of k-tiles each, and a workgroup's k-step is a dependent
+// chain (DMA issue, fragment reads, MFMAs, wait + barrier: ~610 clocks per 64-deep step in gemm_glds.hip, ~880 in its pipelined
+// form inside the step).  With the roles split the chain is gone: a k-step costs what its 16 KB of operands cost the CU's
+// L2 -> LDS path (~400 clocks).  Measured alone (us, ws64 / 64-row family / hipBLASLt): 440 x 2304 x 768 7.2 / 10.4 / 8.3,
+// 440 x 768 x 768 6.5 / 8.4 / 7.2, 868 x 2048 x 512 7.8 / 9.7 / 9.4, weight-gradient form 2304 x 768 x 448 7.7 / 9.4.
+// Each consumer wave owns ONE 32 x 32 fragment (two accumulators: even / odd k-slices).  80 KB of LDS and 97 VGPRs: two workgroups
+// share a CU.  In-launch split-K as in the family (partials through write-through stores, ticket, last arriver sums in split
+// order); RS: the consumer waves of column tile 0 add the row sums of A (one more MFMA against ones per k-slice) = the bias
+// gradient colsum(dy) of a weight-gradient launch.
+#include "gemm_bt.hpp"
+
+namespace vglds {
+
+#ifndef VITAE_WS64_STAGES
+#define VITAE_WS64_STAGES 4         // 64 KB (the epilogue aliases the stages): TWO workgroups per CU, three k-tiles in flight each
+#endif
+constexpr int WS64_SMEM = VITAE_WS64_STAGES * 16384;
+// W2 (round 5, forward form only): the B operand (a weight matrix) comes as TWO bf16 planes, hi = bf16(W) and lo = bf16(W - hi)
+// (p.B / p.B2, same layout): a stage is [A | B hi | B lo] and every k-slice takes two MFMAs, x16 Wlo^T + x16 Whi^T — the weight
+// enters at ~2^-17 instead of 2^-9 while the activations stay bf16.  Why: tools/bf16_rounding_ablation.py — the bf16 schedule's
+// loss error against the fp32 reference is carried by the rounding of the WEIGHTS in the forward (1.3e-4 of 1.5e-4 on the total;
+// activations 9e-6, the whole backward 4e-6), and the decoder's fc1 alone is 1.2e-4 of it.
+template <bool A_KC, bool B_KC, int S, bool RS, bool W2 = false>
+__device__ __forceinline__ void gemm_ws64_body(const GArgs& p, const WsHot& h, const int bid, const int zid, unsigned char* smem) {
+#ifndef VITAE_WS64_PRODUCERS
+#define VITAE_WS64_PRODUCERS 4
+#endif
+    constexpr int BM = 64, BN = 64, NWC = 4, NWP = VITAE_WS64_PRODUCERS;
+    constexpr int A_T = BM * BK * 2, B_T = BN * BK * 2, STG = A_T + (W2 ? 2 : 1) * B_T;
+    constexpr int PA = pieces<BM, A_KC, NWP>(), PB = pieces<BN, B_KC, NWP>(), PT = PA + (W2 ? 2 : 1) * PB;
+    static_assert(!W2 || (A_KC && B_KC && !RS), "two weight planes: the forward form");
+    static_assert(S >= 3 && S <= 5 && (S - 2) * PT <= 63, "stage count");
+    // the XCD-balanced tile map (gemm_bt.hpp)
+    const int T = h.tiles_m * h.tiles_n;
+    const int xq = T >> 3, xr = T & 7, xcd = bid & 7;
+    const int lin = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
+    if ((bid >> 3) >= xq + (xcd < xr ? 1 : 0)) return;
+    const int tn = (h.xcd_m & 1) ? lin % h.tiles_n : lin / h.tiles_m;
+    const int tm = (h.xcd_m & 1) ? lin / h.tiles_n : lin % h.tiles_m;
+    const int m0 = tm * BM, n0 = tn * BN;
+    const int kbeg = zid * h.kps;
+    const int nk = (min(h.K, kbeg + h.kps) - kbeg) / BK;         // >= 2 (launcher)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // tools/ws64_phase_probe.py: s_memtime stamps of consumer wave 0 (slots 0-7) and producer wave 4 (8-15) of every workgroup,
+    // 16 per workgroup indexed by its position in the launch (blockIdx.x + gridDim.x * blockIdx.z)
+    auto stamp = [&](int i) {
+        if ((h.xcd_m & 2) && (threadIdx.x & 255) == 0) p.dbg[((long)blockIdx.z * gridDim.x + blockIdx.x) * 16 + i] = __builtin_amdgcn_s_memtime();
+    };
+    if (wave >= NWC) {
+        // ---------------- producers ----------------
+        const int pw = wave - NWC;
+        stamp(8);
+        auto issue_tile = [&](int t, int stage) {
+            unsigned char* dst = smem + stage * STG;
+            const int k0 = kbeg + t * BK;
+#pragma unroll
+            for (int j = 0; j < PA; ++j) dma_piece<BM, A_KC, NWP>(h.A, h.lda, h.M, m0, k0, dst, pw, lane, j);
+#pragma unroll
+            for (int j = 0; j < PB; ++j) dma_piece<BN, B_KC, NWP>(h.B, h.ldb, h.N, n0, k0, dst + A_T, pw, lane, j);
+            if constexpr (W2) {
+#pragma unroll
+                for (int j = 0; j < PB; ++j) dma_piece<BN, B_KC, NWP>(h.B2, h.ldb, h.N, n0, k0, dst + A_T + B_T, pw, lane, j);
+            }
+        };
+        const int npre = min(S - 1, nk);
+        for (int t = 0; t < npre; ++t) issue_tile(t, t);
+        stamp(9);                                                        // prologue issued
+        wait_tiles<S, PT>(npre - 1);
+        stamp(10);                                                       // first k-tile landed
+        wg_barrier();                                                    // B_0
+        int stage = npre % S;
+#pragma unroll 1
+        for (int t = 0; t + 1 < nk; ++t) {
+            if (t + S - 1 < nk) {
+                issue_tile(t + S - 1, stage);
+                stage = stage + 1 == S ? 0 : stage + 1;
+            }
+            wait_tiles<S, PT>(min(t + S - 1, nk - 1) - (t + 1));
+            wg_barrier();                                                // B_{t+1}
+        }
+        stamp(11);                                                       // last k-tile handed over
+        return;
+    }
+    // ---------------- consumers ----------------
+    const int wm = wave >> 1, wn = wave & 1;
+    const int l31 = lane & 31, hi = lane >> 5;
+    f32x16 acc[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[h][i] = 0.f;
+    const bool rowsum = RS && p.a_rowsum != nullptr && tn == 0 && wn == 0;   // wave-uniform; every k-split adds its share
+    f32x16 accx;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) accx[i] = 0.f;
+    bf16x8 ones;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
+    bf16x8 fa[BK / 16], fb[BK / 16], fb2[W2 ? BK / 16 : 1];
+    constexpr int RK = (A_KC ? 1 : 2) + (W2 ? 2 : 1) * (B_KC ? 1 : 2);
+    auto rd = [&](const unsigned char* TA, auto kk_c) {
+        constexpr int kk = decltype(kk_c)::value;
+        fa[kk] = frag_asm<BM, A_KC>(TA, wm * 32, kk, lane);
+        fb[kk] = frag_asm<BN, B_KC>(TA + A_T, wn * 32, kk, lane);
+        if constexpr (W2) fb2[kk] = frag_asm<BN, B_KC>(TA + A_T + B_T, wn * 32, kk, lane);
+    };
+    auto mm = [&](auto kk_c) {
+        constexpr int kk = decltype(kk_c)::value;
+        frag_tie(fa[kk]); frag_tie(fb[kk]);
+        if constexpr (W2) {                                              // the small term first
+            frag_tie(fb2[kk]);
+            acc[kk & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk], fb2[kk], acc[kk & 1], 0, 0, 0);
+        }
+        acc[kk & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk], fb[kk], acc[kk & 1], 0, 0, 0);
+        if constexpr (RS) {
+            if (rowsum) accx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk], ones, accx, 0, 0, 0);
+        }
+    };
+    // the bias of this wave's four-column groups, fetched now (after the loop it would cost an exposed memory latency)
+    const int nq = n0 + wn * 32 + 4 * (lane % 8);
+    f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
+    if (p.bias && nq < p.N) bias4 = *reinterpret_cast<const f32x4*>(p.bias + nq);
+    stamp(0);
+    wg_barrier();                                                        // B_0
+    stamp(1);
+    ws64_consume<2 * RK, S, STG>(smem, nk, rd, mm);
+    if (RS && rowsum && l31 == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + wm * 32 + crow(r, hi);
+            if (m < p.M) atomicAdd(p.a_rowsum + m, accx[r]);
+        }
+    }
+    // The tail (gemm_wsx3_body has a copy without the stamps).  As one shared function it changed the code of every kernel built on
+    // either body (pairs of ds_write_b32 merged in the parked quadrant, other compare forms all over the epilogue, other register
+    // counts on seven of the ten kernels): written out in both.
+    stamp(2);                                                            // k-loop done
+    f32x16 accs[1][1];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) accs[0][0][i] = acc[0][i] + acc[1][i];
+    // the epilogue's LDS (4 KB per wave, the split-K flag, the norm shares) ALIASES the stages: every consumer is past its last
+    // fragment read at this barrier, every DMA has landed, and the producers are gone — so the whole LDS budget is prefetch depth
+    __syncthreads();
+    float* Tw = reinterpret_cast<float*>(smem) + wave * 1024;
+    if (p.splits > 1) {
+        // (the producers have left: these barriers count the four consumer waves only)
+        const int tile = p.tile0 + tm * p.tiles_n + tn;
+        float* part = p.ws + VITAE_GLDS_TICKETS + (long)tile * p.splits * (BM * BN);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(part, 0, p.splits * (BM * BN * 4), 0x00020000);
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        const int toff = (int)threadIdx.x * 16;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 v = {accs[0][0][4 * g], accs[0][0][4 * g + 1], accs[0][0][4 * g + 2], accs[0][0][4 * g + 3]};
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (zid * 4 + g) * (256 * 16) + toff, 0, 16);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        int* flag = reinterpret_cast<int*>(smem + 4 * 4096);
+        if (threadIdx.x == 0) *flag = __hip_atomic_fetch_add(reinterpret_cast<int*>(p.ws) + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        stamp(3);                                                        // partials parked, ticket taken
+        if (*flag != p.splits - 1) return;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) accs[0][0][i] = 0.f;
+#pragma unroll 1
+        for (int sp0 = 0; sp0 < p.splits; sp0 += 4) {
+            f32x4 v[4][4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int sp = min(sp0 + u, p.splits - 1);               // (clamped: a repeated load, never added)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    v[u][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (sp * 4 + g) * (256 * 16) + toff, 0, 16));
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (sp0 + u < p.splits) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) accs[0][0][4 * g + e] += v[u][g][e];
+                }
+        }
+        if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<int*>(p.ws) + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    stamp(4);                                                            // epilogue starts
+    bt_park_quadrant<1, 1, 1>(accs, lane, Tw);
+    __builtin_amdgcn_wave_barrier();
+    float sqs = 0.f;
+    { f32x4 cz = {0.f, 0.f, 0.f, 0.f}; bt_wave_epilogue<1, 1>(p, bt_epilogue_kind(p), m0 + wm * 32, n0 + wn * 32, Tw, lane, sqs, bias4, cz, false); }
+    stamp(5);                                                            // stores issued
+    if (p.sqacc) {                                                       // one atomic per workgroup (see bt_tail)
+        sqs = wave_sum(sqs);
+        float* red = reinterpret_cast<float*>(smem + 4 * 4096 + 64);
+        if (lane == 0) red[wave] = sqs;
+        __syncthreads();
+        if (threadIdx.x == 0) atomicAdd(sq_slot(p), (double)((red[0] + red[1]) + (red[2] + red[3])));
+    }
+    if (p.dbg) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(6); }      // stores drained
+}
+
+template <bool A_KC, bool B_KC>
+__global__ __launch_bounds__(64 * (4 + VITAE_WS64_PRODUCERS), 2) void gemm_ws64_kernel(WS_HOT_PARAMS, const GArgs p) {
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[WS64_SMEM];      // the ONLY LDS object
+    const WsHot h = WS_HOT_FROM_PARAMS;
+    gemm_ws64_body<A_KC, B_KC, VITAE_WS64_STAGES, false>(p, h, blockIdx.x, blockIdx.z, smem);
+}
+
+void ws64_launch(const GArgs& p, int a_kc, int b_kc, hipStream_t st) {
+    const dim3 grid(8 * cdiv((long)p.tiles_m * p.tiles_n, 8), 1, p.splits), block(64 * (4 + VITAE_WS64_PRODUCERS));
+    if (a_kc && b_kc) hipLaunchKernelGGL((gemm_ws64_kernel<true, true>), grid, block, 0, st, WS_HOT_ARGS(p), p);
+    else if (a_kc && !b_kc) hipLaunchKernelGGL((gemm_ws64_kernel<true, false>), grid, block, 0, st, WS_HOT_ARGS(p), p);
+    else hipLaunchKernelGGL((gemm_ws64_kernel<false, false>), grid, block, 0, st, WS_HOT_ARGS(p), p);
+}
+
+constexpr int WS64W2_STAGES = 3;           // [A | B hi | B lo] = 24 KB per stage: three stages = 72 KB, two workgroups per CU
+__global__ __launch_bounds__(64 * (4 + VITAE_WS64_PRODUCERS), 2) void gemm_ws64_w2_kernel(WS_HOT_PARAMS, const GArgs p) {
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[WS64W2_STAGES * 24576];      // the ONLY LDS object
+    gemm_ws64_body<true, true, WS64W2_STAGES, false, true>(p, WS_HOT_FROM_PARAMS, blockIdx.x, blockIdx.z, smem);
+}
+
+// p: a complete forward-form descriptor (both operands k-contiguous, vec_epi set, p.B2 = the lo plane, p.splits k-ranges)
+int ws64_w2_launch(GArgs p, hipStream_t st) {
+    if (!p.vec_epi || !p.B2 || p.a_rowsum || (p.K % BK) || p.splits < 1) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (!bt_k_ranges(p.K, 2, p.splits, p.k_per_split)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    p.tiles_m = cdiv(p.M, 64); p.tiles_n = cdiv(p.N, 64); p.tile0 = 0;
+    if (p.splits > 1 && (!p.ws || (long)p.tiles_m * p.tiles_n > VITAE_GLDS_TICKETS || p.epi == VITAE_EPI_GELU)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    const dim3 grid(8 * cdiv((long)p.tiles_m * p.tiles_n, 8), 1, p.splits), block(64 * (4 + VITAE_WS64_PRODUCERS));
+    hipLaunchKernelGGL(gemm_ws64_w2_kernel, grid, block, 0, st, WS_HOT_ARGS(p), p);
+    return vitae_launch_status();
+}
+
+// Backward of one Linear as ONE launch of such workgroups: the first nb1 * p1.splits blocks compute the input gradient
+// dx = epi(dy W) (A = dy k-contiguous, B = W row-contiguous; its long reduction cut into p1.splits), the rest the weight gradient
+// dW (+)= dy^T x (both row-contiguous; RS: + colsum(dy)).
+// The leading scalars are what either half needs before its first DMA (WsHot), in 14 dwords so that all of them are preloaded: the
+// halves of one Linear's backward SHARE dy (A of both), its leading dimension, the leading dimension of W / x, the width K of the layer
+// (N of both), and the weight gradient's rows are the input gradient's reduction length (ws64_pair_launch checks exactly that).
+//   packed = nb1 | p1.splits << 20 | p1.xcd_m << 24 | p2.xcd_m << 25 | (dbg set) << 26
+template <bool RS>
+__global__ __launch_bounds__(64 * (4 + VITAE_WS64_PRODUCERS), 2) void gemm_ws64_pair_kernel(const __bf16* A, const __bf16* B1, const __bf16* B2, int lda, int ldb,
+                                                                                           int M1, int N1, int K1, int K2, int kps1, int packed,
+                                                                                           const GArgs p1, const GArgs p2) {
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[WS64_SMEM];
+    const int nb1 = packed & 0xfffff, splits1 = (packed >> 20) & 15, dbg2 = (packed >> 25) & 2;
+    if ((int)blockIdx.x < nb1 * splits1) {
+        const WsHot h{A, B1, nullptr, lda, ldb, M1, N1, K1, (M1 + 63) >> 6, (N1 + 63) >> 6, ((packed >> 24) & 1) | dbg2, kps1};
+        gemm_ws64_body<true, false, VITAE_WS64_STAGES, false>(p1, h, blockIdx.x % nb1, blockIdx.x / nb1, smem);
+    } else {
+        const WsHot h{A, B2, nullptr, lda, ldb, K1, N1, K2, (K1 + 63) >> 6, (N1 + 63) >> 6, ((packed >> 25) & 1) | dbg2, K2};
+        gemm_ws64_body<false, false, VITAE_WS64_STAGES, RS>(p2, h, blockIdx.x - nb1 * splits1, 0, smem);
+    }
+}
+
+// p1 / p2: complete descriptors of the two halves (vec_epi set, K % 64 == 0); p1.splits k-ranges of >= 2 k-tiles each
+int ws64_pair_launch(GArgs p1, GArgs p2, hipStream_t st) {
+    if (!p1.vec_epi || !p2.vec_epi || (p1.K % BK) || (p2.K % BK) || p2.K < 2 * BK || p1.a_rowsum) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (p1.splits < 1) p1.splits = 1;
+    if (!bt_k_ranges(p1.K, 2, p1.splits, p1.k_per_split)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    p1.tiles_m = cdiv(p1.M, 64); p1.tiles_n = cdiv(p1.N, 64); p1.tile0 = 0;
+    p2.tiles_m = cdiv(p2.M, 64); p2.tiles_n = cdiv(p2.N, 64); p2.tile0 = 0;
+    p2.k_per_split = p2.K; p2.splits = 1;
+    if (p1.splits > 1 && (!p1.ws || (long)p1.tiles_m * p1.tiles_n > VITAE_GLDS_TICKETS)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    const int nb1 = 8 * cdiv((long)p1.tiles_m * p1.tiles_n, 8), nb2 = 8 * cdiv((long)p2.tiles_m * p2.tiles_n, 8);
+    const dim3 grid(nb1 * p1.splits + nb2), block(64 * (4 + VITAE_WS64_PRODUCERS));
+    // what the kernel's leading scalars assume (the two halves of ONE Linear's backward: gemm_ws64_pair_kernel)
+    if (p1.A != p2.A || p1.lda != p2.lda || p1.ldb != p2.ldb || p2.M != p1.K || p2.N != p1.N || nb1 >= (1 << 20) || p1.splits > 15 ||
+        p1.lda >= (1L << 31) || p1.ldb >= (1L << 31)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    const int packed = nb1 | p1.splits << 20 | (p1.xcd_m & 1) << 24 | (p2.xcd_m & 1) << 25 | ((p1.dbg || p2.dbg) ? 1 << 26 : 0);
+    if (p2.a_rowsum) hipLaunchKernelGGL((gemm_ws64_pair_kernel<true>), grid, block, 0, st, p1.A, p1.B, p2.B, (int)p1.lda, (int)p1.ldb, p1.M, p1.N, p1.K,
+                                        p2.K, p1.k_per_split, packed, p1, p2);
+    else hipLaunchKernelGGL((gemm_ws64_pair_kernel<false>), grid, block, 0, st, p1.A, p1.B, p2.B, (int)p1.lda, (int)p1.ldb, p1.M, p1.N, p1.K,
+                            p2.K, p1.k_per_split, packed, p1, p2);
+    return vitae_launch_status();
+}
+
+}  // namespace vglds

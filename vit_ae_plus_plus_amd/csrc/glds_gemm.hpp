@@ -34,7 +34,7 @@ struct GArgs {
     int exact = 0;               // GELU / GELU' through erff (the fp32-grade modes) instead of the 1.5e-7 polynomial
     int auxd = 0;                // aux holds GELU'(pre-activation) (VITAE_EPI_AUX_DERIV): GELU saves it, GELU' multiplies by it
     const __bf16* B2 = nullptr;  // second plane of the B operand (lo = bf16(W - bf16(W)), same layout as B): vitae_gemm_glds_w2
-    int a_kwrap = 0;             // > 0: the A operand is a_kwrap wide and k wraps (gemm_bt.hip: a_wrap) — two-plane weights side by side in B
+    int a_kwrap = 0;             // > 0: the A operand is a_kwrap wide and k wraps (gemm_bt.hpp: a_wrap) — two-plane weights side by side in B
     long long* dbg;      // optional (tools/gemm_phase_probe.py): 8 s_memtime stamps per workgroup
     int xcd_m;           // 0: an XCD owns column tiles tn = xcd (mod 8) and walks every row tile (its L2 holds 1/8 of B and all
                          // of A); 1: it owns row tiles tm = xcd (mod 8) instead — picked when A is the larger operand
@@ -115,19 +115,19 @@ __device__ __forceinline__ float epilogue_frag(const GArgs& p, const float (&v)[
     return csum;
 }
 
-// gemm_bt.hip: the big-tile kernels (id 0: 256x256 on 8 waves; 3: 128x128 on 4 waves; wave-specialised: 4: 128x128, 5: 64x64).  `p` is a complete
-// descriptor of ONE unsplit problem; tiles_m / tiles_n are set by the launcher.
+// gemm_bt.hip: the big-tile kernels (id 0: 256x256 on 8 waves; 3: 128x128 on 4 waves; wave-specialised, gemm_ws.hip / gemm_ws64.hip: 4: 128x128,
+// 5: 64x64, 6: 128x256).  `p` is a complete descriptor of ONE unsplit problem; tiles_m / tiles_n are set by the launcher.
 bool bt_tile_dims(int id, int& bm, int& bn);
 int bt_launch(GArgs p, int a_kc, int b_kc, int id, hipStream_t st);
 int bt_wgrad_group_launch(GArgs* ps, int n, int splits, hipStream_t st, int kind);
-// gemm_bt.hip: input gradient + weight gradient of one Linear as ONE launch of wave-specialised 64 x 64 workgroups (tile id 5)
+// gemm_ws64.hip: input gradient + weight gradient of one Linear as ONE launch of wave-specialised 64 x 64 workgroups (tile id 5)
 int ws64_pair_launch(GArgs p1, GArgs p2, hipStream_t st);
-// ... the same as persistent workgroups walking a tile queue with the tiles pipelined across each other (round 6)
+// gemm_ws64q.hip: the same as persistent workgroups walking a tile queue with the tiles pipelined across each other (round 6)
 int ws64q_pair_launch(GArgs p1, GArgs p2, hipStream_t st);
-// gemm_bt.hip: fp32 operands split into bf16 hi + lo by the producer waves of a wave-specialised 64 x 64 workgroup (fp32x3 mode);
+// gemm_wsx3.hip: fp32 operands split into bf16 hi + lo by the producer waves of a wave-specialised 64 x 64 workgroup (fp32x3 mode);
 // p.A / p.B point at FLOATS here, p.K any multiple of 4
 int wsx3_launch(GArgs p, int a_kc, int b_kc, hipStream_t st);
-// gemm_bt.hip: forward form with a two-plane (hi + lo) weight operand on the wave-specialised 64 x 64 workgroup
+// gemm_ws64.hip: forward form with a two-plane (hi + lo) weight operand on the wave-specialised 64 x 64 workgroup
 int ws64_w2_launch(GArgs p, hipStream_t st);
 int wsx3_slots();
 
