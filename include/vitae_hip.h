@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define VITAE_ABI_VERSION 56
+#define VITAE_ABI_VERSION 57
 
 /* matrix-core arithmetic of the dense contractions */
 #define VITAE_PREC_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32 (the reference's precision, autocast off at utils/train_one_epoch.py:50) */
@@ -626,6 +626,21 @@ int vitae_grad_sqnorm_multi(const long long* table_host, const long long* table_
 int vitae_adamw_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
                       const int* chunks_dev, long n_chunks, long chunk, const float* group_lr_dev, const float* group_wd_dev, int n_groups,
                       double beta1, double beta2, double eps, double max_norm, float* state, double* acc, float* norm_out, void* stream);
+/* ---- bf16 weight shadows (ABI 57): vitae_adamw_multi_shadow, vitae_ema_multi_shadow and vitae_lars_multi_shadow are their siblings
+ * with a shadow column.  shadow_host / shadow_dev: n_entries device addresses of bf16 destinations, entry t beside table entry t,
+ * 0 = that tensor has no shadow; host copy judged by the launcher, device copy read by the kernel, as the table.  Every fp32 result
+ * is the sibling's, bit for bit (same kernels compiled on a flag, same grids, same order of every sum, no atomics added); beside it
+ * shadow[i] = (__bf16)x for every fp32 parameter value x the call stores (pm; p; p), the conversion of vitae_cast_bf16, so that
+ * afterwards shadow == vitae_cast_bf16(parameter) bit for bit, NaN, infinities, -0, denormals and ties included.  A tensor is
+ * streamed 16 bytes at a time (8-byte shadow stores of four bf16) when its fp32 addresses are 16-byte aligned AND its shadow address
+ * is 8-byte aligned, else element by element (2-byte shadow stores); a shadow that is only 2-byte aligned is legal.  Where the
+ * sibling writes nothing (vitae_adamw_multi on a non-finite norm) no shadow is written either; counters behave as the sibling's.
+ * Refusals beyond the sibling's, nothing written and nothing launched: exactly one of shadow_host / shadow_dev NULL, an odd shadow
+ * address.  Both NULL: the call is the sibling's. */
+int vitae_adamw_multi_shadow(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                             const int* chunks_dev, long n_chunks, long chunk, const float* group_lr_dev, const float* group_wd_dev,
+                             int n_groups, double beta1, double beta2, double eps, double max_norm, float* state, double* acc,
+                             float* norm_out, const long long* shadow_host, const long long* shadow_dev, void* stream);
 
 /* ---- MoCo v3 (ABI 55, csrc/moco.hip): other_baselines/mocov3/moco/builder.py and optimizer.py around the encoder.
  * vitae_ema_multi / vitae_lars_multi walk the table + chunk list of the multi-tensor AdamW above (same layout, same host / device
@@ -636,6 +651,10 @@ int vitae_adamw_multi(const long long* table_host, const long long* table_dev, l
  * aligned, element by element otherwise. */
 int vitae_ema_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
                     const int* chunks_dev, long n_chunks, long chunk, double m, void* stream);
+/* (ABI 57) the same, and shadow[i] = (__bf16)pm[i] of the new pm for every entry that lists a shadow: see "bf16 weight shadows" above */
+int vitae_ema_multi_shadow(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                           const int* chunks_dev, long n_chunks, long chunk, double m, const long long* shadow_host,
+                           const long long* shadow_dev, void* stream);
 /* vitae_lars_multi (optimizer.py:18-43), two launches: entry = (p, g, mu, flags, n, group); flags bit 0 = "p.ndim > 1".
  *   (1) per chunk of a flagged tensor: sum p^2 and sum (g + wd p)^2 in double -> ws[2 c], ws[2 c + 1];
  *   (2) per tensor the partials are summed in chunk order (deterministic); q = trust |p| / |dp| when both norms > 0, else 1;
@@ -647,6 +666,10 @@ int vitae_ema_multi(const long long* table_host, const long long* table_dev, lon
 int vitae_lars_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
                      const int* chunks_dev, long n_chunks, long chunk, const float* group_hp_dev, int n_groups, double* ws,
                      void* stream);
+/* (ABI 57) the same, and shadow[i] = (__bf16)p[i] of the new p for every entry that lists a shadow; only launch (2) differs */
+int vitae_lars_multi_shadow(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                            const int* chunks_dev, long n_chunks, long chunk, const float* group_hp_dev, int n_groups, double* ws,
+                            const long long* shadow_host, const long long* shadow_dev, void* stream);
 /* Both InfoNCE terms of builder.py:63-75,98 and their gradients, three launches: rows normalised as F.normalize (x / max(|x|, 1e-12)),
  * logits = qn kn^T / T, cross-entropy against the diagonal (row maximum subtracted), mean over N, times 2 T, summed over the pairs
  * (q1, k2) and (q2, k1).  loss[0] and dq1 / dq2 [N, C] for unit upstream gradient; the clamped norm is a constant; k gets none.

@@ -22,7 +22,13 @@ groups with (a) ``torch.optim.AdamW``, (b) ``torch.optim.AdamW(fused=True)`` whe
 ``optim.MultiTensorAdamW``, the three in turns inside this process, with and without ``clip_grad``; then the optimiser part alone
 (norm [+ clipping] + step on the gradients of the last backward) and ``MultiTensorAdamW`` alone at several chunk lengths.
 
-    python tools/finetune_bench.py optimizer [--batch 4]"""
+    python tools/finetune_bench.py optimizer [--batch 4]
+
+``optimizer --shadow 0,1``: the bf16 weight shadows (``VITAE_WEIGHT_SHADOW``) off against on: two models with ``MultiTensorAdamW``, one
+stepped with the switch at 0 and one with it at 1, in alternating windows of ``--inner`` steps (default 5) in this process, ``--reps``
+windows each (default 9); median (min .. max) of the whole step and of the optimiser alone (28 B per parameter off, 30 B on).
+
+    python tools/finetune_bench.py optimizer --shadow 0,1 [--batch 4] [--reps 9] [--inner 5]"""
 import os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -50,6 +56,7 @@ def _usage(msg):
 
 
 ACTIVATIONS, BATCH = _option('--activations'), _option('--batch')
+SHADOW, REPS_OPT, INNER_OPT = _option('--shadow'), _option('--reps'), _option('--inner')
 ROWS = ARGV or ['step', 'mixup', 'criterion', 'evaluate']
 KNOWN = ('step', 'mixup', 'criterion', 'evaluate', 'optimizer')
 if [r for r in ROWS if r not in KNOWN]:
@@ -58,6 +65,10 @@ if ACTIVATIONS is not None and ACTIVATIONS != 'bf16':
     _usage(f"--activations takes 'bf16' (got {ACTIVATIONS!r})")
 if ACTIVATIONS and ROWS != ['step'] or BATCH and ROWS not in (['step'], ['optimizer']):
     _usage('--activations / --batch go with the step row alone: finetune_bench.py step --activations bf16 [--batch B]')
+if SHADOW is not None and (SHADOW != '0,1' or ROWS != ['optimizer']):
+    _usage("--shadow takes '0,1' and goes with the optimizer row: finetune_bench.py optimizer --shadow 0,1 [--batch B] [--reps R] [--inner I]")
+if (REPS_OPT or INNER_OPT) and not SHADOW:
+    _usage('--reps / --inner go with --shadow')
 if BATCH is not None and (not (ACTIVATIONS or ROWS == ['optimizer']) or not BATCH.isdigit() or int(BATCH) < 1):
     _usage('--batch takes a positive integer and goes with --activations or with the optimizer row')
 
@@ -285,7 +296,70 @@ def optimizer_rows():
         del runs, m, opt, x
 
 
-if 'optimizer' in ROWS:
+def shadow_rows():
+    """MultiTensorAdamW with the bf16 weight shadows off and on, in alternating windows: whole step and optimiser alone."""
+    from vit_ae_plus_plus_amd.optim import MultiTensorAdamW
+    from vit_ae_plus_plus_amd.utils.misc import NativeScalerWithGradNormCount
+    reps, inner = int(REPS_OPT or 9), int(INNER_OPT or 5)
+    scaler = NativeScalerWithGradNormCount()
+    crit = torch.nn.CrossEntropyLoss()
+
+    def windows(fns, inner):
+        tss = [[] for _ in fns]
+        for _ in range(reps):
+            for fn, ts in zip(fns, tss):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    fn()
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e3 / inner)
+        return [(statistics.median(ts), min(ts), max(ts)) for ts in tss]
+
+    print(f'shadow: {reps} alternating windows of {inner} steps per variant; ms per step, median (min .. max)', flush=True)
+    print('| batch | clip_grad | what | shadow off | shadow on | on / off | spread of off |')
+    print('|---|---|---|---|---|---|---|')
+    for B in ([int(BATCH)] if BATCH else [4, 16]):
+        x = torch.randn(B, 4, 96, 96, 96, device='cuda')
+        y = torch.randint(0, 2, (B,), device='cuda')
+        runs = []
+        for switch in ('0', '1'):       # each model lives under one setting: its slots are never current (off) or always (on)
+            m = VisionTransformer3D(volume_size=96, patch_size=16, in_chans=4, num_classes=2, global_pool=True, precision='bf16',
+                                    activations='bf16', drop_path_rate=0.1).cuda().train()
+            torch.nn.init.normal_(m.head.weight, std=0.02)
+            runs.append((switch, m, MultiTensorAdamW(param_groups_lrd(m, 0.05, m.no_weight_decay(), 0.75), lr=1e-5)))
+        n_params = sum(p.numel() for p in runs[0][1].parameters())
+        for clip in (None, 1.0):
+            def whole(switch, m, opt):
+                def f():
+                    os.environ['VITAE_WEIGHT_SHADOW'] = switch
+                    opt.zero_grad(set_to_none=True)
+                    scaler(crit(m(x), y), opt, clip_grad=clip, parameters=m.parameters())
+                return f
+
+            def alone(switch, m, opt):      # on the gradients the last whole step left behind
+                def f():
+                    os.environ['VITAE_WEIGHT_SHADOW'] = switch
+                    opt.norm_clip_step(clip)
+                return f
+
+            for fn in [whole(*r) for r in runs] * 3:
+                fn()
+            (a, b) = windows([whole(*r) for r in runs], inner)
+            (c, d) = windows([alone(*r) for r in runs], 4 * inner)
+            fmt = lambda t: f'{t[0]:.3f} ({t[1]:.3f} .. {t[2]:.3f})'
+            print(f'| {B} | {clip} | whole step | {fmt(a)} | {fmt(b)} | {b[0] / a[0]:.4f} | {a[2] - a[1]:.3f} |', flush=True)
+            print(f'| {B} | {clip} | optimiser alone, {n_params / 1e6:.1f} M parameters | {fmt(c)} = {28 * n_params / c[0] / 1e9:.2f} TB/s at 28 B | '
+                  f'{fmt(d)} = {30 * n_params / d[0] / 1e9:.2f} TB/s at 30 B | {d[0] / c[0]:.4f} | {c[2] - c[1]:.3f} |', flush=True)
+        for switch, m, opt in runs:
+            print(f'shadow {switch} B={B}: applied {opt.applied_steps()} steps, skipped {opt.skipped_steps()}', flush=True)
+        del runs, x
+        torch.cuda.empty_cache()
+
+
+if 'optimizer' in ROWS and SHADOW:
+    shadow_rows()
+elif 'optimizer' in ROWS:
     optimizer_rows()
 if 'step' in ROWS and ACTIVATIONS:
     act16_rows()

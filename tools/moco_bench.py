@@ -14,6 +14,13 @@ Then the three launch groups alone on the tensors of that step, with achieved by
 EMA 12 B per parameter (read pm, pb; write pm), LARS 8 B (norm pass: p, g) + 20 B (update pass: p, g, mu read; p, mu written) per
 parameter of a scaled tensor, 20 B of an unscaled one; the loss 4 N C * 4 B in + 2 N C * 4 B out.  ``vitae_adamw_multi`` reaches
 4.6 TB/s on the fine-tuning model (LABNOTES.md) — the yardstick for the two streaming groups.
+
+    python tools/moco_bench.py shadow=0,1 [batch=4,16] [routes=act16] [reps=9] [inner=5] [depth=12]
+
+``shadow=0,1``: the bf16 weight shadows (``VITAE_WEIGHT_SHADOW``) off against on instead of kernels against torch statements: two
+kernel models, one always stepped with the switch at 0 and one with it at 1 (so the slots of the first are never current and those of
+the second always), in the same alternating windows; then the EMA and LARS launch groups alone, off (12 B; 8 + 20 B per parameter)
+against on (14 B; 8 + 22 B for the weights that have a slot: the GEMM weights of the encoders).
 """
 import os
 import statistics
@@ -113,11 +120,64 @@ def step_fn(model, opt, scaler, x1, x2):
     return f
 
 
+def under(switch, fn):
+    """fn with VITAE_WEIGHT_SHADOW = switch (the updaters read it at call time)"""
+    def f():
+        os.environ['VITAE_WEIGHT_SHADOW'] = switch
+        fn()
+    return f
+
+
+def shadow_main(batches, routes, reps, inner, depth):
+    from vit_ae_plus_plus_amd import shadow
+    fmt = lambda t: f'{t[0]:.3f} ({t[1]:.3f} .. {t[2]:.3f})'
+    print('| route | batch / view | shadow off ms (min .. max) | shadow on ms (min .. max) | on / off | spread of off ms |')
+    print('|---|---|---|---|---|---|')
+    alone = []
+    for route in routes:
+        for B in batches:
+            g = torch.Generator().manual_seed(B)
+            x1 = torch.randn(B, 4, 96, 96, 96, generator=g).cuda()
+            x2 = torch.randn(B, 4, 96, 96, 96, generator=g).cuda()
+            a, b = make(route, depth, True), make(route, depth, True)
+            fa, fb = under('0', step_fn(*a, x1, x2)), under('1', step_fn(*b, x1, x2))
+            for _ in range(3):
+                fa(); fb()
+            off, on = windows([fa, fb], reps, inner)
+            print(f'| {route} | {B} | {fmt(off)} | {fmt(on)} | {on[0] / off[0]:.4f} | {off[2] - off[1]:.3f} |', flush=True)
+            if not alone:
+                n_all = sum(p.numel() for p in a[0].base_encoder.parameters())
+                slot = lambda ps: sum(p.numel() for p in ps if shadow.slot_for(p) is not None and shadow.slot_for(p).current())
+                train = [p for p in b[0].parameters() if p.grad is not None]
+                n_scaled, n_plain = sum(p.numel() for p in train if p.ndim > 1), sum(p.numel() for p in train if p.ndim <= 1)
+                s_ema, s_lars = slot(b[0].momentum_encoder.parameters()), slot(train)
+                e0, e1 = windows([under('0', lambda: a[0]._update_momentum_encoder(M)), under('1', lambda: b[0]._update_momentum_encoder(M))], reps, 20)
+                by0, by1 = 12 * n_all, 12 * n_all + 2 * s_ema
+                alone.append(f'| EMA, {n_all / 1e6:.1f} M parameters ({s_ema / 1e6:.1f} M with a slot) | {fmt(e0)} | {fmt(e1)} | {by0 / 1e6:.0f} / {by1 / 1e6:.0f} MB | '
+                             f'{by0 / e0[0] / 1e9:.2f} / {by1 / e1[0] / 1e9:.2f} |')
+                l0, l1 = windows([under('0', a[1].step), under('1', b[1].step)], reps, 20)
+                by0 = 28 * n_scaled + 20 * n_plain
+                by1 = by0 + 2 * s_lars
+                alone.append(f'| LARS, {(n_scaled + n_plain) / 1e6:.1f} M parameters ({s_lars / 1e6:.1f} M with a slot) | {fmt(l0)} | {fmt(l1)} | {by0 / 1e6:.0f} / {by1 / 1e6:.0f} MB | '
+                             f'{by0 / l0[0] / 1e9:.2f} / {by1 / l1[0] / 1e9:.2f} |')
+            del a, b, fa, fb
+            torch.cuda.empty_cache()
+    print()
+    print('| launch group alone | shadow off ms (min .. max) | shadow on ms (min .. max) | bytes moved off / on | TB/s off / on |')
+    print('|---|---|---|---|---|')
+    for row in alone:
+        print(row)
+
+
 def main():
     batches = [int(b) for b in _option('batch', '4,16').split(',')]
-    routes = _option('routes', 'bf16,act16').split(',')
+    routes = _option('routes', 'act16' if _option('shadow', '') else 'bf16,act16').split(',')
     reps, inner, depth = int(_option('reps', '9')), int(_option('inner', '5')), int(_option('depth', '12'))
     print(f'# device {torch.cuda.get_device_name(0)}; reps {reps} x {inner} steps per window; depth {depth}')
+    if _option('shadow', ''):
+        if _option('shadow', '') != '0,1':
+            sys.exit("moco_bench.py: shadow takes '0,1'")
+        return shadow_main(batches, routes, reps, inner, depth)
     print('| route | batch / view | kernels ms (min .. max) | torch statements ms (min .. max) | ratio |')
     print('|---|---|---|---|---|')
     for route in routes:

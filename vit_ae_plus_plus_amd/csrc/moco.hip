@@ -1,4 +1,4 @@
-// MoCo v3 around the encoder (ABI 55): the momentum update, LARS and the InfoNCE loss of other_baselines/mocov3/moco as
+// MoCo v3 around the encoder (ABI 55; bf16 weight shadows: ABI 57): the momentum update, LARS and the InfoNCE loss of other_baselines/mocov3/moco as
 // launches over whole parameter lists / whole batches.  All memory- or latency-bound: wave reductions, no MFMA.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -26,19 +26,40 @@ __device__ __forceinline__ void block_sum2_f64(double& a, double& b, double (*re
     b = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
 }
 
+// ---- bf16 shadows (ABI 57): the update that stores a new fp32 weight also stores its bf16 copy, with cast_bf16_kernel's conversion
+// (gemm_bf16.hip), so the encoders' GEMMs need no cast launch afterwards.  SH is a compile-time flag: without it the bodies below are
+// the kernels of ABI 55, instruction for instruction.  shadow[t]: device address of tensor t's bf16 copy, 0 = none.
+template <bool SH>
+__device__ __forceinline__ __bf16* shadow_of(const long long* shadow, int t, long off) {
+    if constexpr (SH) {
+        const long long a = shadow[t];
+        return a ? reinterpret_cast<__bf16*>(a) + off : nullptr;
+    }
+    return nullptr;
+}
+__device__ __forceinline__ void shadow_store4(__bf16* sh, long i, const f32x4 v) {
+    bf16x4 h;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) h[k] = (__bf16)v[k];
+    reinterpret_cast<bf16x4*>(sh)[i] = h;             // one 8-byte store
+}
+
 // ---- momentum update: pm <- pm m + pb (1 - m)
-template <int U>
-__global__ __launch_bounds__(256) void ema_multi_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks, long n_chunks,
-                                                        long chunk, float m, float omm) {
+template <int U, bool SH>
+__device__ __forceinline__ void ema_multi_body(const MultiEntry* table, const int* chunks, long n_chunks,
+                                               long chunk, float m, float omm, const long long* shadow) {
     for (long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-        const MultiEntry e = table[chunks[2 * c]];
+        const int t = chunks[2 * c];
+        const MultiEntry e = table[t];
         const long off = (long)chunks[2 * c + 1] * chunk;
         const long len = e.n - off < chunk ? e.n - off : chunk;
         float* pm = e.p + off;
         const float* pb = e.g + off;
+        __bf16* sh = shadow_of<SH>(shadow, t, off);
         long done = 0;
-        // chunk and off are multiples of 4: the chunk is 16-byte aligned exactly when the tensor's base addresses are
-        if (!(((uintptr_t)pm | (uintptr_t)pb) & 15)) {
+        // chunk and off are multiples of 4: the chunk is 16-byte aligned exactly when the tensor's base addresses are (and its shadow
+        // 8-byte aligned exactly when the shadow's base address is)
+        if (!(((uintptr_t)pm | (uintptr_t)pb) & 15) && !((uintptr_t)sh & 7)) {
             const long n4 = len / 4;
             f32x4* pm4 = reinterpret_cast<f32x4*>(pm);
             const f32x4* pb4 = reinterpret_cast<const f32x4*>(pb);
@@ -53,13 +74,32 @@ __global__ __launch_bounds__(256) void ema_multi_kernel(const MultiEntry* __rest
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (i0 + u * 256 >= n4) break;
-                    pm4[i0 + u * 256] = a[u] * m + b[u] * omm;
+                    const f32x4 r = a[u] * m + b[u] * omm;
+                    pm4[i0 + u * 256] = r;
+                    if (SH && sh) shadow_store4(sh, i0 + u * 256, r);
                 }
             }
             done = n4 * 4;
         }
-        for (long i = done + threadIdx.x; i < len; i += 256) pm[i] = pm[i] * m + pb[i] * omm;
+        for (long i = done + threadIdx.x; i < len; i += 256) {
+            const float r = pm[i] * m + pb[i] * omm;
+            pm[i] = r;
+            if (SH && sh) sh[i] = (__bf16)r;
+        }
     }
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void ema_multi_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks, long n_chunks,
+                                                        long chunk, float m, float omm) {
+    ema_multi_body<U, false>(table, chunks, n_chunks, chunk, m, omm, nullptr);
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void ema_multi_shadow_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks,
+                                                               long n_chunks, long chunk, float m, float omm,
+                                                               const long long* __restrict__ shadow) {
+    ema_multi_body<U, true>(table, chunks, n_chunks, chunk, m, omm, shadow);
 }
 
 // ---- LARS, launch 1: per chunk of a scaled tensor, sum p^2 and sum (g + wd p)^2 in double
@@ -96,9 +136,10 @@ __global__ __launch_bounds__(256) void lars_norm_kernel(const MultiEntry* __rest
 }
 
 // ---- LARS, launch 2: the trust ratio of the chunk's tensor from the partials (in chunk order), then the update
-template <int U>
-__global__ __launch_bounds__(256) void lars_step_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks, long n_chunks,
-                                                        long chunk, const float* __restrict__ hp, int n_groups, const double* __restrict__ ws) {
+template <int U, bool SH>
+__device__ __forceinline__ void lars_step_body(const MultiEntry* table, const int* chunks, long n_chunks,
+                                               long chunk, const float* hp, int n_groups, const double* ws,
+                                               const long long* shadow) {
     __shared__ double red[4][2];
     int cur_t = -1;
     float q = 1.f;
@@ -121,8 +162,9 @@ __global__ __launch_bounds__(256) void lars_step_kernel(const MultiEntry* __rest
         float* p = e.p + off;
         const float* g = e.g + off;
         float* mu = e.m + off;
+        __bf16* sh = shadow_of<SH>(shadow, t, off);
         long done = 0;
-        if (!(((uintptr_t)p | (uintptr_t)g | (uintptr_t)mu) & 15)) {
+        if (!(((uintptr_t)p | (uintptr_t)g | (uintptr_t)mu) & 15) && !((uintptr_t)sh & 7)) {
             const long n4 = len / 4;
             f32x4* p4 = reinterpret_cast<f32x4*>(p);
             f32x4* m4 = reinterpret_cast<f32x4*>(mu);
@@ -140,7 +182,9 @@ __global__ __launch_bounds__(256) void lars_step_kernel(const MultiEntry* __rest
                     const f32x4 dp = scaled ? (gv[u] + pv[u] * wd) * q : gv[u];
                     const f32x4 mn = mv[u] * mom + dp;
                     m4[i0 + u * 256] = mn;
-                    p4[i0 + u * 256] = pv[u] - mn * lr;
+                    const f32x4 pn = pv[u] - mn * lr;
+                    p4[i0 + u * 256] = pn;
+                    if (SH && sh) shadow_store4(sh, i0 + u * 256, pn);
                 }
             }
             done = n4 * 4;
@@ -150,9 +194,24 @@ __global__ __launch_bounds__(256) void lars_step_kernel(const MultiEntry* __rest
             const float dp = scaled ? (g[i] + pe * wd) * q : g[i];
             const float mn = mu[i] * mom + dp;
             mu[i] = mn;
-            p[i] = pe - mn * lr;
+            const float pn = pe - mn * lr;
+            p[i] = pn;
+            if (SH && sh) sh[i] = (__bf16)pn;
         }
     }
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void lars_step_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks, long n_chunks,
+                                                        long chunk, const float* __restrict__ hp, int n_groups, const double* __restrict__ ws) {
+    lars_step_body<U, false>(table, chunks, n_chunks, chunk, hp, n_groups, ws, nullptr);
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void lars_step_shadow_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks,
+                                                               long n_chunks, long chunk, const float* __restrict__ hp, int n_groups,
+                                                               const double* __restrict__ ws, const long long* __restrict__ shadow) {
+    lars_step_body<U, true>(table, chunks, n_chunks, chunk, hp, n_groups, ws, shadow);
 }
 
 // ---- InfoNCE.  ws: double rowloss[2 N] | double denom[4 N] (max(|x|, 1e-12) of the rows of q1, k2, q2, k1)
@@ -254,6 +313,13 @@ int multi_check(const long long* table, long n_entries, const int* chunks, long 
     return VITAE_OK;
 }
 
+// the shadow column of a *_shadow call, judged on its host copy like the table: every address even (a bf16 address)
+int shadow_check(const long long* shadow_host, long n_entries) {
+    for (long t = 0; t < n_entries; ++t)
+        if (shadow_host[t] & 1) return VITAE_ERR_INVALID_ARG;
+    return VITAE_OK;
+}
+
 }  // namespace
 
 extern "C" int vitae_ema_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
@@ -266,6 +332,22 @@ extern "C" int vitae_ema_multi(const long long* table_host, const long long* tab
     const long blocks = n_chunks < 512 ? n_chunks : 512;
     hipLaunchKernelGGL(ema_multi_kernel<4>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const MultiEntry*>(table_dev), chunks_dev, n_chunks, chunk, (float)m, (float)(1. - m));
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_ema_multi_shadow(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                                      const int* chunks_dev, long n_chunks, long chunk, double m, const long long* shadow_host,
+                                      const long long* shadow_dev, void* stream) {
+    if (!shadow_host && !shadow_dev) return vitae_ema_multi(table_host, table_dev, n_entries, chunks_host, chunks_dev, n_chunks, chunk, m, stream);
+    if (!shadow_host || !shadow_dev) return VITAE_ERR_INVALID_ARG;
+    if (!(m >= 0.0 && m <= 1.0)) return VITAE_ERR_INVALID_ARG;
+    const int rc = multi_check(table_host, n_entries, chunks_host, n_chunks, chunk, 0, false);
+    if (rc != VITAE_OK || n_entries == 0 || n_chunks == 0) return rc;
+    if (!table_dev || !chunks_dev || shadow_check(shadow_host, n_entries) != VITAE_OK) return VITAE_ERR_INVALID_ARG;
+    // vitae_ema_multi's grid: 14 bytes per element where a shadow is listed
+    const long blocks = n_chunks < 512 ? n_chunks : 512;
+    hipLaunchKernelGGL(ema_multi_shadow_kernel<4>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const MultiEntry*>(table_dev), chunks_dev, n_chunks, chunk, (float)m, (float)(1. - m), shadow_dev);
     return vitae_launch_status();
 }
 
@@ -286,6 +368,27 @@ extern "C" int vitae_lars_multi(const long long* table_host, const long long* ta
                        n_groups, ws);
     hipLaunchKernelGGL(lars_step_kernel<4>, dim3((int)sb), dim3(256), 0, (hipStream_t)stream, table, chunks_dev, n_chunks, chunk,
                        group_hp_dev, n_groups, ws);
+    return vitae_launch_status();
+}
+
+extern "C" int vitae_lars_multi_shadow(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                                       const int* chunks_dev, long n_chunks, long chunk, const float* group_hp_dev, int n_groups, double* ws,
+                                       const long long* shadow_host, const long long* shadow_dev, void* stream) {
+    if (!shadow_host && !shadow_dev)
+        return vitae_lars_multi(table_host, table_dev, n_entries, chunks_host, chunks_dev, n_chunks, chunk, group_hp_dev, n_groups, ws, stream);
+    if (!shadow_host || !shadow_dev) return VITAE_ERR_INVALID_ARG;
+    if (n_groups < 1 || n_groups > VITAE_MULTI_MAX_GROUPS || !group_hp_dev) return VITAE_ERR_INVALID_ARG;
+    const int rc = multi_check(table_host, n_entries, chunks_host, n_chunks, chunk, n_groups, true);
+    if (rc != VITAE_OK || n_entries == 0 || n_chunks == 0) return rc;
+    if (!table_dev || !chunks_dev || !ws || ((uintptr_t)ws & 7)) return VITAE_ERR_INVALID_ARG;
+    if (shadow_check(shadow_host, n_entries) != VITAE_OK) return VITAE_ERR_INVALID_ARG;
+    const MultiEntry* table = reinterpret_cast<const MultiEntry*>(table_dev);
+    // vitae_lars_multi's two launches and grids; only the second one writes, and only it knows the shadows (22 bytes per element there)
+    const long nb = n_chunks < 1024 ? n_chunks : 1024, sb = n_chunks < 256 ? n_chunks : 256;
+    hipLaunchKernelGGL(lars_norm_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, table, chunks_dev, n_chunks, chunk, group_hp_dev,
+                       n_groups, ws);
+    hipLaunchKernelGGL(lars_step_shadow_kernel<4>, dim3((int)sb), dim3(256), 0, (hipStream_t)stream, table, chunks_dev, n_chunks, chunk,
+                       group_hp_dev, n_groups, ws, shadow_dev);
     return vitae_launch_status();
 }
 

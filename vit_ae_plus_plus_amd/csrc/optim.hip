@@ -347,13 +347,16 @@ __global__ __launch_bounds__(256) void grad_sqnorm_multi_kernel(const MultiEntry
     if (threadIdx.x == 0) atomicAdd(gradsq_slot(acc), red[0] + red[1] + red[2] + red[3]);
 }
 
-// adamw_kernel's data path (U independent 16-byte groups per thread, non-temporal moments and gradients) over one chunk at a time
-template <int U>
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks, long n_chunks,
-                                                          long chunk, const float* __restrict__ group_lr,
-                                                          const float* __restrict__ group_wd, float omb1, float b2, float omb2, float eps,
-                                                          float max_norm, float* __restrict__ state, double* __restrict__ acc,
-                                                          float* __restrict__ norm_out) {
+// adamw_kernel's data path (U independent 16-byte groups per thread, non-temporal moments and gradients) over one chunk at a time.
+// SH (ABI 57): shadow[t] is the device address of tensor t's bf16 copy (0: none), written with cast_bf16_kernel's conversion from the
+// parameter values just stored — 16-byte path when the shadow is 8-byte aligned too, else element by element.  A compile-time flag:
+// without it the body is the kernel of ABI 54, instruction for instruction.
+template <int U, bool SH>
+__device__ __forceinline__ void adamw_multi_body(const MultiEntry* table, const int* chunks, long n_chunks,
+                                                 long chunk, const float* group_lr,
+                                                 const float* group_wd, float omb1, float b2, float omb2, float eps,
+                                                 float max_norm, float* state, double* acc,
+                                                 float* norm_out, const long long* shadow) {
     __shared__ int last;
     // the norm straight from the accumulator, as adamw_kernel's gacc gate: every wave sums the spread slots itself
     double q = acc[VITAE_ACC_SQ_BASE + (threadIdx.x & 63) * VITAE_ACC_SQ_STRIDE];
@@ -369,7 +372,8 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const MultiEntry* __re
         const float sq_bc2 = sqrtf(bc2);
         const float gs = max_norm > 0.f ? fminf(1.f, max_norm / (gn + 1e-6f)) : 1.f;      // torch.nn.utils.clip_grad_norm_
         for (long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-            const MultiEntry e = table[chunks[2 * c]];
+            const int t_idx = chunks[2 * c];
+            const MultiEntry e = table[t_idx];
             const long off = (long)chunks[2 * c + 1] * chunk;
             const long len = e.n - off < chunk ? e.n - off : chunk;
             const float lr = group_lr[e.group];
@@ -377,9 +381,15 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const MultiEntry* __re
             float* p = e.p + off;
             const float* g = e.g + off;
             float *m = e.m + off, *v = e.v + off;
+            __bf16* sh = nullptr;
+            if constexpr (SH) {
+                const long long a = shadow[t_idx];
+                if (a) sh = reinterpret_cast<__bf16*>(a) + off;
+            }
             long done = 0;
-            // chunk and off are multiples of 4: the chunk is 16-byte aligned exactly when the tensor's base addresses are
-            if (!(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15)) {
+            // chunk and off are multiples of 4: the chunk is 16-byte aligned exactly when the tensor's base addresses are (and its
+            // shadow 8-byte aligned exactly when the shadow's base address is)
+            if (!(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) && !((uintptr_t)sh & 7)) {
                 const long n4 = len / 4;
                 f32x4* p4 = reinterpret_cast<f32x4*>(p);
                 for (long i0 = threadIdx.x; i0 < n4; i0 += U * 256) {
@@ -408,6 +418,12 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const MultiEntry* __re
                         p4[i] = pp[u];
                         state4_st<float>(m, i, mm[u]);
                         state4_st<float>(v, i, vv[u]);
+                        if (SH && sh) {
+                            bf16x4 h;
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) h[k] = (__bf16)pp[u][k];
+                            reinterpret_cast<bf16x4*>(sh)[i] = h;
+                        }
                     }
                 }
                 done = n4 * 4;
@@ -416,6 +432,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const MultiEntry* __re
                 float pe = p[i], me = m[i], ve = v[i];
                 adamw_element(pe, me, ve, g[i], gs, decay, omb1, b2, omb2, step, sq_bc2, eps);
                 p[i] = pe; m[i] = me; v[i] = ve;
+                if (SH && sh) sh[i] = (__bf16)pe;
             }
         }
     }
@@ -436,6 +453,25 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const MultiEntry* __re
             state[finite ? VITAE_MULTI_STATE_STEP : VITAE_MULTI_STATE_SKIPPED] += 1.f;
         }
     }
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks, long n_chunks,
+                                                          long chunk, const float* __restrict__ group_lr,
+                                                          const float* __restrict__ group_wd, float omb1, float b2, float omb2, float eps,
+                                                          float max_norm, float* __restrict__ state, double* __restrict__ acc,
+                                                          float* __restrict__ norm_out) {
+    adamw_multi_body<U, false>(table, chunks, n_chunks, chunk, group_lr, group_wd, omb1, b2, omb2, eps, max_norm, state, acc, norm_out, nullptr);
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void adamw_multi_shadow_kernel(const MultiEntry* __restrict__ table, const int* __restrict__ chunks,
+                                                                 long n_chunks, long chunk, const float* __restrict__ group_lr,
+                                                                 const float* __restrict__ group_wd, float omb1, float b2, float omb2,
+                                                                 float eps, float max_norm, float* __restrict__ state,
+                                                                 double* __restrict__ acc, float* __restrict__ norm_out,
+                                                                 const long long* __restrict__ shadow) {
+    adamw_multi_body<U, true>(table, chunks, n_chunks, chunk, group_lr, group_wd, omb1, b2, omb2, eps, max_norm, state, acc, norm_out, shadow);
 }
 
 }  // namespace
@@ -631,6 +667,28 @@ extern "C" int vitae_adamw_multi(const long long* table_host, const long long* t
     hipLaunchKernelGGL(adamw_multi_kernel<8>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const MultiEntry*>(table_dev), chunks_dev, n_chunks, chunk, group_lr_dev, group_wd_dev, (float)(1.0 - beta1), (float)beta2,
                        (float)(1.0 - beta2), (float)eps, (float)max_norm, state, acc, norm_out);
+    return vitae_launch_status();
+}
+
+// ... and the bf16 copy of every updated tensor that lists one (ABI 57): 30 instead of 28 bytes per parameter, no cast launch afterwards
+extern "C" int vitae_adamw_multi_shadow(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                                        const int* chunks_dev, long n_chunks, long chunk, const float* group_lr_dev, const float* group_wd_dev,
+                                        int n_groups, double beta1, double beta2, double eps, double max_norm, float* state, double* acc,
+                                        float* norm_out, const long long* shadow_host, const long long* shadow_dev, void* stream) {
+    if (!shadow_host && !shadow_dev)
+        return vitae_adamw_multi(table_host, table_dev, n_entries, chunks_host, chunks_dev, n_chunks, chunk, group_lr_dev, group_wd_dev, n_groups,
+                                 beta1, beta2, eps, max_norm, state, acc, norm_out, stream);
+    if (!shadow_host || !shadow_dev) return VITAE_ERR_INVALID_ARG;
+    if (n_groups < 1 || n_groups > VITAE_MULTI_MAX_GROUPS || !group_lr_dev || !group_wd_dev) return VITAE_ERR_INVALID_ARG;
+    const int rc = multi_check(table_host, n_entries, chunks_host, n_chunks, chunk, n_groups, true);
+    if (rc != VITAE_OK || n_entries == 0 || n_chunks == 0) return rc;
+    if (!table_dev || !chunks_dev || !state || !acc || !norm_out) return VITAE_ERR_INVALID_ARG;
+    for (long t = 0; t < n_entries; ++t)
+        if (shadow_host[t] & 1) return VITAE_ERR_INVALID_ARG;          // not a bf16 address
+    const long blocks = n_chunks < 256 ? n_chunks : 256;               // vitae_adamw_multi's grid
+    hipLaunchKernelGGL(adamw_multi_shadow_kernel<8>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const MultiEntry*>(table_dev), chunks_dev, n_chunks, chunk, group_lr_dev, group_wd_dev, (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), (float)eps, (float)max_norm, state, acc, norm_out, shadow_dev);
     return vitae_launch_status();
 }
 

@@ -25,6 +25,7 @@ import torch
 
 from ._abi import CONSTS as _C, VitaeError, lib
 from ._launch import EPI_AUX_BF16, EPI_AUX_DERIV, EPI_DGELU, EPI_GELU, EPI_NONE, PREC, fit_split, pad64 as _pad64, ptr as _ptr
+from .shadow import store_of
 
 _EMBED = ('cls_token', 'pos_embed', 'patch_embed.proj.weight', 'patch_embed.proj.bias')
 
@@ -53,7 +54,7 @@ def act16_refusal_for(module, precision, in_chans=None):
 
 class HipEncoder:
     """Sequences the encoder kernels for one ``VisionTransformer3D`` instance (weights are read from the module's parameters at call
-    time; bf16 copies are cached per parameter version) and runs them for inference.  The launch helpers of both routes live here;
+    time; bf16 copies live in the model's shadow store, shadow.py) and runs them for inference.  The launch helpers of both routes live here;
     ``self.buf`` holds the split-K scratch of the route in use (``'ws'``: generic launchers, ``'ws16'``: LDS-DMA family, whose ticket
     words start as zero and are left zero by every launch) and, for inference, the cached activation buffers."""
 
@@ -63,7 +64,6 @@ class HipEncoder:
         lib.load()
         self.m = module
         self.precision, self.prec = precision, PREC[precision]
-        self._w16: Dict[str, Tuple[int, torch.Tensor]] = {}
         self._B = None          # (batch size, device) the inference buffers were made for
         self.buf: Dict[str, torch.Tensor] = {}
         self._split: Dict[Tuple, int] = {}
@@ -78,14 +78,14 @@ class HipEncoder:
         return p
 
     def _bf16(self, name: str) -> int:
+        """Address of the bf16 copy of parameter ``name``: its slot in the model's shadow store (shadow.py), cast here when the slot does
+        not hold the parameter as it is now.  The multi-tensor updaters keep a current slot current, so a steady step casts nothing."""
         p = self._param(name)
-        ent = self._w16.get(name)
-        if ent is None or ent[0] != p._version or ent[1].device != p.device:
-            t = torch.empty(p.numel(), dtype=torch.bfloat16, device=p.device)
-            lib.vitae_cast_bf16(p.data_ptr(), t.data_ptr(), p.numel(), self.stream)
-            ent = (p._version, t)
-            self._w16[name] = ent
-        return ent[1].data_ptr()
+        slot = store_of(self.m).slot(p)
+        if not slot.current():
+            lib.vitae_cast_bf16(p.data_ptr(), slot.address(), p.numel(), self.stream)
+            slot.mark()
+        return slot.address()
 
     # ------------------------------------------------------------------ workspace
     def _alloc(self, B: int):

@@ -303,6 +303,7 @@ class VisionTransformer3D(nn.Module):
         self._activations = None
         self._encoder = None
         self._trainer = None
+        self._shadow = None         # shadow.ShadowStore: bf16 weight slots shared by the inference encoder and the trainer, made on first use
         self.init_weights(weight_init)
         if activations is not None:
             self.set_precision(self._precision, activations=activations)
@@ -349,6 +350,9 @@ class VisionTransformer3D(nn.Module):
         self._activations = activations
         self._encoder = None
         self._trainer = None
+        if self._shadow is not None:        # the bf16 weight slots go with the encoders that read them (shadow.py)
+            self._shadow.drop()
+            self._shadow = None
 
     def _encoder_params(self):
         return [(n, p) for n, p in self.named_parameters() if not n.startswith('head.')]

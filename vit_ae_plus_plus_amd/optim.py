@@ -14,6 +14,7 @@ import torch
 
 from . import _abi
 from ._abi import VitaeError, lib
+from .shadow import mark_current, pack_words, shadow_column
 
 
 class FusedAdamW:
@@ -390,7 +391,7 @@ class MultiTensorAdamW(torch.optim.AdamW):
         d = self._dev
         if d is None or d.get('key') != key:
             chunks = multi_chunk_list(lengths, self._chunk)
-            d = self._buffers(device, nt * ew + ng + (chunks.size + 1) // 2)
+            d = self._buffers(device, nt * ew + ng + nt + (chunks.size + 1) // 2)       # (room for a shadow column)
             d['key'], d['chunks'] = key, chunks
         d = self._buffers(device, 0)
         chunks = d['chunks']
@@ -400,16 +401,18 @@ class MultiTensorAdamW(torch.optim.AdamW):
             d['events'][slot].synchronize()      # the step that last used this slot, RING steps ago, has finished reading it
         pinned, table = d['pinned'][slot], d['table'][slot]
         host = pinned.numpy()
-        host[:nt * ew].reshape(nt, ew)[:] = multi_table(p_ptrs, g_ptrs, m_ptrs, v_ptrs, lengths, groups)
-        # [table | lr of every group, wd of every group (fp32) | chunk list (int32 pairs)], in 64-bit words
-        hyper = host[nt * ew:nt * ew + ng].view(np.float32)
-        hyper[:ng] = [float(g['lr']) for g in self.param_groups]
-        hyper[ng:] = [float(g['weight_decay']) for g in self.param_groups]
-        words = nt * ew + ng
-        if d['keys'][slot] != key:               # the chunk list travels with the table only when this slot does not hold it yet
-            host[words:].view(np.int32)[:chunks.size] = chunks.reshape(-1)
+        # bf16 slots that hold these parameters as they are now get the new weights in the same pass (shadow.py); a slot that is stale
+        # (a load_state_dict since the last forward, ...) is not listed, so this step cannot validate it
+        column, listed = shadow_column(params)
+        # [table | lr of every group, wd of every group (fp32) | shadow column, if any | chunk list (int32 pairs)], in 64-bit words
+        hyper = [float(g['lr']) for g in self.param_groups] + [float(g['weight_decay']) for g in self.param_groups]
+        front = pack_words(multi_table(p_ptrs, g_ptrs, m_ptrs, v_ptrs, lengths, groups), hyper, column)
+        words = base = front.size
+        host[:base] = front
+        if d['keys'][slot] != (key, base):       # the chunk list travels with the table only when this slot does not hold it yet
+            host[base:].view(np.int32)[:chunks.size] = chunks.reshape(-1)
             words += (chunks.size + 1) // 2
-            d['keys'][slot] = key
+            d['keys'][slot] = (key, base)
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream()
             table[:words].copy_(pinned[:words], non_blocking=True)
@@ -419,17 +422,22 @@ class MultiTensorAdamW(torch.optim.AdamW):
             norm = torch.empty((), dtype=torch.float32, device=device)
             th, td = pinned.data_ptr(), table.data_ptr()
             lrd = td + 8 * nt * ew
-            ch, cd = th + 8 * (nt * ew + ng), td + 8 * (nt * ew + ng)
+            ch, cd = th + 8 * base, td + 8 * base
             lib.vitae_grad_sqnorm_multi(th, td, nt, ch, cd, len(chunks), self._chunk, d['acc'].data_ptr(), stream.cuda_stream)
-            lib.vitae_adamw_multi(th, td, nt, ch, cd, len(chunks), self._chunk, lrd, lrd + 4 * ng, ng,
-                                  float(g0['betas'][0]), float(g0['betas'][1]), float(g0['eps']),
-                                  float(max_norm) if max_norm is not None else 0.0, d['state'].data_ptr(), d['acc'].data_ptr(),
-                                  norm.data_ptr(), stream.cuda_stream)
+            args = (th, td, nt, ch, cd, len(chunks), self._chunk, lrd, lrd + 4 * ng, ng,
+                    float(g0['betas'][0]), float(g0['betas'][1]), float(g0['eps']),
+                    float(max_norm) if max_norm is not None else 0.0, d['state'].data_ptr(), d['acc'].data_ptr(), norm.data_ptr())
+            if column is None:
+                lib.vitae_adamw_multi(*args, stream.cuda_stream)
+            else:                                # the column is the last nt words in front of the chunk list
+                lib.vitae_adamw_multi_shadow(*args, th + 8 * (base - nt), td + 8 * (base - nt), stream.cuda_stream)
             ev = d['events'][slot] or torch.cuda.Event()
             ev.record(stream)
             d['events'][slot] = ev
-        # the kernels wrote through raw pointers: autograd (and every cache keyed on p._version, encoder.HipEncoder._bf16) must see it
+        # the kernels wrote through raw pointers: autograd (and everything keyed on p._version, the bf16 slots of shadow.py) must see it
         torch.autograd.graph.increment_version(params)
+        # a skipped step wrote neither the weights nor the slots: the listed slots hold the (unchanged) weights at the new version too
+        mark_current(listed)
         return norm
 
     def step(self, closure=None):

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from ...._abi import VitaeError, lib
 from ....model.vit import _stream, hip_linear
+from ....shadow import mark_current, shadow_column
 from .optimizer import TableRing, ema_table, fp32_on_device
 
 
@@ -228,13 +229,20 @@ class MoCo(nn.Module):
                 raise VitaeError('_update_momentum_encoder: the two encoders must hold the same parameters on one device')
         lengths = [pm.numel() for _, pm in pairs]
         table = ema_table([pm.data_ptr() for _, pm in pairs], [pb.data_ptr() for pb, _ in pairs], lengths)
+        # bf16 slots of the momentum encoder that hold its weights as they are now get the new ones in the same pass (shadow.py)
+        column, listed = shadow_column([pm for _, pm in pairs])
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream()
-            a = self._ema_ring.send(device, table, lengths)
-            lib.vitae_ema_multi(a['th'], a['td'], a['nt'], a['ch'], a['cd'], a['nc'], a['chunk'], float(m), stream.cuda_stream)
+            a = self._ema_ring.send(device, table, lengths, shadow=column)
+            if a['sh'] is None:
+                lib.vitae_ema_multi(a['th'], a['td'], a['nt'], a['ch'], a['cd'], a['nc'], a['chunk'], float(m), stream.cuda_stream)
+            else:
+                lib.vitae_ema_multi_shadow(a['th'], a['td'], a['nt'], a['ch'], a['cd'], a['nc'], a['chunk'], float(m), a['sh'], a['sd'],
+                                           stream.cuda_stream)
             self._ema_ring.done(a['slot'], stream)
-        # written through raw pointers: the momentum encoder's bf16 weight cache is keyed on p._version
+        # written through raw pointers: whatever is keyed on p._version must see it; the listed slots hold the new version
         torch.autograd.graph.increment_version([pm for _, pm in pairs])
+        mark_current(listed)
 
     def contrastive_loss(self, q, k):
         """InfoNCE of one (query, key) pair: rows normalised, logits q k^T / T, cross-entropy against the diagonal, times 2 T."""

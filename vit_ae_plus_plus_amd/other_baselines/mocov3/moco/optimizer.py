@@ -11,6 +11,7 @@ import torch
 
 from ...._abi import CONSTS, VitaeError, lib
 from ....optim import multi_chunk_list
+from ....shadow import mark_current, pack_words, shadow_column
 
 
 class TableRing:
@@ -35,32 +36,31 @@ class TableRing:
             d['keys'] = [None] * self.RING
         return d
 
-    def send(self, device, table: np.ndarray, lengths, hyper=()):
-        """table: int64 [n_tensors, VITAE_MULTI_ENTRY_WORDS]; hyper: floats sent behind it.  -> dict of the launchers' arguments
-        (``th`` / ``td``: table on host / device, ``ch`` / ``cd``: chunk list, ``hd``: hyper-parameters on the device, ``nt``, ``nc``, ``chunk``)
-        and ``slot`` for ``done()``.  Call with the device current; follow the launches with ``done(slot)``."""
+    def send(self, device, table: np.ndarray, lengths, hyper=(), shadow=None):
+        """table: int64 [n_tensors, VITAE_MULTI_ENTRY_WORDS]; hyper: floats sent behind it; shadow: int64 [n_tensors] bf16 addresses sent
+        behind those (``shadow.shadow_column``; None: no column).  -> dict of the launchers' arguments (``th`` / ``td``: table on host /
+        device, ``ch`` / ``cd``: chunk list, ``hd``: hyper-parameters on the device, ``sh`` / ``sd``: shadow column or None, ``nt``, ``nc``,
+        ``chunk``) and ``slot`` for ``done()``.  Call with the device current; follow the launches with ``done(slot)``."""
         chunk = int(CONSTS['VITAE_MULTI_CHUNK'])
         nt, ew = table.shape
-        nh = (len(hyper) + 1) // 2                 # 64-bit words of hyper-parameters
+        front = pack_words(table, hyper, shadow)       # everything in front of the chunk list: one copy carries it all
+        base = front.size
         key = (chunk, device, tuple(lengths))
         d = self._d
         if d is None or d['device'] != device or d['key'] != key:
             chunks = multi_chunk_list(lengths, chunk)
-            d = self._buffers(device, nt * ew + nh + 64 + (chunks.size + 1) // 2)
+            d = self._buffers(device, base + nt + 64 + (chunks.size + 1) // 2)
             d['key'], d['chunks'] = key, chunks
         chunks = d['chunks']
-        base = nt * ew + nh
-        if base + (chunks.size + 1) // 2 > d['words']:     # more hyper-parameters than when the buffers were sized
-            d = self._buffers(device, base + 64 + (chunks.size + 1) // 2)
+        if base + (chunks.size + 1) // 2 > d['words']:     # more words in front than when the buffers were sized
+            d = self._buffers(device, base + nt + 64 + (chunks.size + 1) // 2)
         slot = d['seq'] % self.RING
         d['seq'] += 1
         if d['events'][slot] is not None:
             d['events'][slot].synchronize()        # the call that last used this slot, RING calls ago, has finished reading it
         pinned, dev = d['pinned'][slot], d['table'][slot]
         host = pinned.numpy()
-        host[:nt * ew].reshape(nt, ew)[:] = table
-        if nh:
-            host[nt * ew:base].view(np.float32)[:len(hyper)] = hyper
+        host[:base] = front
         words = base
         if d['keys'][slot] != (key, base):
             host[base:].view(np.int32)[:chunks.size] = chunks.reshape(-1)
@@ -68,8 +68,10 @@ class TableRing:
             d['keys'][slot] = (key, base)
         dev[:words].copy_(pinned[:words], non_blocking=True)
         th, td = pinned.data_ptr(), dev.data_ptr()
+        so = 8 * (base - nt)                       # the shadow column is the last nt words in front of the chunk list
         return {'th': th, 'td': td, 'nt': nt, 'ch': th + 8 * base, 'cd': td + 8 * base, 'nc': len(chunks), 'chunk': chunk,
-                'hd': td + 8 * nt * ew, 'slot': slot}
+                'hd': td + 8 * nt * ew, 'sh': None if shadow is None else th + so, 'sd': None if shadow is None else td + so,
+                'slot': slot}
 
     def done(self, slot, stream):
         d = self._d
@@ -150,14 +152,21 @@ class LARS(torch.optim.Optimizer):
         if not params:
             return loss
         hyper = [float(g[k]) for k in ('lr', 'weight_decay', 'momentum', 'trust_coefficient') for g in self.param_groups]
+        column, listed = shadow_column(params)      # bf16 slots that hold these parameters as they are now (shadow.py)
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream()
-            a = self._ring.send(device, lars_table(p_ptrs, g_ptrs, mu_ptrs, scaled, lengths, groups), lengths, hyper)
+            a = self._ring.send(device, lars_table(p_ptrs, g_ptrs, mu_ptrs, scaled, lengths, groups), lengths, hyper, column)
             if self._ws is None or self._ws.device != device or self._ws.numel() < 2 * a['nc']:
                 self._ws = torch.empty(2 * a['nc'], dtype=torch.float64, device=device)
-            lib.vitae_lars_multi(a['th'], a['td'], a['nt'], a['ch'], a['cd'], a['nc'], a['chunk'], a['hd'], ng, self._ws.data_ptr(),
-                                 stream.cuda_stream)
+            if a['sh'] is None:
+                lib.vitae_lars_multi(a['th'], a['td'], a['nt'], a['ch'], a['cd'], a['nc'], a['chunk'], a['hd'], ng, self._ws.data_ptr(),
+                                     stream.cuda_stream)
+            else:
+                lib.vitae_lars_multi_shadow(a['th'], a['td'], a['nt'], a['ch'], a['cd'], a['nc'], a['chunk'], a['hd'], ng,
+                                            self._ws.data_ptr(), a['sh'], a['sd'], stream.cuda_stream)
             self._ring.done(a['slot'], stream)
-        # the kernels wrote through raw pointers: autograd and every cache keyed on p._version (the encoders' bf16 weights) must see it
+        # the kernels wrote through raw pointers: autograd and everything keyed on p._version must see it; the bf16 slots listed above
+        # were written in the same pass and hold the new version
         torch.autograd.graph.increment_version(params)
+        mark_current(listed)
         return loss
