@@ -700,6 +700,26 @@ int vitae_moco_loss(const float* q1, const float* k2, const float* q2, const flo
 #define VITAE_CONV3D_WGRAD_CHUNK 4096 /* rows of M per partial of vitae_conv3d_bwd_weight */
 long vitae_conv3d_packed_elems(int Cout, int Cin, int kd, int kh, int kw, int transposed);
 int vitae_conv3d_pack_weight(const float* w, void* w16, int Cout, int Cin, int kd, int kh, int kw, int transposed, void* stream);
+/* Every convolution operand of a network in one launch (added under ABI 57; resnet.ConvPackStore).
+ *   table   n_entries entries of VITAE_CONV3D_PACK_ENTRY_WORDS 64-bit words: w (device address of torch's fp32 [Cout, Cin, kd, kh, kw]),
+ *           w16 (device address of the bf16 destination, 16-byte aligned, vitae_conv3d_packed_elems(...) elements), Cout, Cin, kd, kh,
+ *           kw, transposed.  Each destination is written bit for bit as vitae_conv3d_pack_weight writes it, zero tails included.
+ *   chunks  the destinations laid end to end in table order and cut every VITAE_CONV3D_PACK_CHUNK elements: per chunk a pair of ints
+ *           (entry, offset / 8) = where the chunk begins.  A workgroup walks on into the following entries, so an entry may begin and
+ *           end anywhere inside a chunk.  (A packed size is a multiple of 16: a 16-byte group of 8 never straddles two entries or rows.)
+ *           vitae_conv3d_pack_multi_chunks counts the chunks of a host table (0: the table is refused);
+ *           vitae_conv3d_pack_multi_chunk_list fills chunks_host (n_chunks must be that count).  Both run on the host alone.
+ * Table and chunk list are passed twice, as for the multi-tensor tables: *_host is judged by the launcher before the launch, *_dev is
+ * what the kernel reads (the caller enqueued the copy on `stream`).  Refused, nothing written: VITAE_ERR_INVALID_ARG for n_entries <= 0, a
+ * NULL array, a NULL w or w16, Cout or Cin <= 0, transposed outside {0, 1}, a chunk list that is not the table's; VITAE_ERR_UNSUPPORTED_SHAPE
+ * for a w16 that is not 16-byte aligned, a geometry vitae_conv3d_pack_weight refuses, a total above VITAE_CONV3D_PACK_MAX_ELEMS. */
+#define VITAE_CONV3D_PACK_ENTRY_WORDS 8
+#define VITAE_CONV3D_PACK_CHUNK 4096
+#define VITAE_CONV3D_PACK_MAX_ELEMS 8589934592 /* 2^33: offset / 8 and the chunk count fit an int */
+long vitae_conv3d_pack_multi_chunks(const long long* table_host, long n_entries);
+int vitae_conv3d_pack_multi_chunk_list(const long long* table_host, long n_entries, int* chunks_host, long n_chunks);
+int vitae_conv3d_pack_weights_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                                    const int* chunks_dev, long n_chunks, void* stream);
 /* [N, C, D, H, W] fp32 -> [N, D, H, W, C] bf16 (the network input) */
 int vitae_to_channels_last_bf16(const float* x, void* x16, int N, int C, int D, int H, int W, void* stream);
 /* y[m, co] = sum_{tap, ci} x16[src(m, tap), ci] w16[co, tap, ci]; y fp32 and / or y_bf16 (at least one) */

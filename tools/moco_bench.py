@@ -21,6 +21,13 @@ parameter of a scaled tensor, 20 B of an unscaled one; the loss 4 N C * 4 B in +
 kernel models, one always stepped with the switch at 0 and one with it at 1 (so the slots of the first are never current and those of
 the second always), in the same alternating windows; then the EMA and LARS launch groups alone, off (12 B; 8 + 20 B per parameter)
 against on (14 B; 8 + 22 B for the weights that have a slot: the GEMM weights of the encoders).
+
+    python tools/moco_bench.py arch=resnet [batch=4,16] [reps=9] [inner=5]
+
+``arch=resnet``: ``MoCo_ResNet`` over ResNet-10 on 96^3 x 4 channels (mlp_dim 4096, dim 256), the script's default ``--arch``, through
+the same loop.  Two tables, each of two models alternating in this process: kernels against the torch statements (as above), and the
+convolution operand store (``resnet.ConvPackStore``, one ``vitae_conv3d_pack_weights_multi`` launch per encoder and step) against a pack
+per convolution call (``VITAE_CONV_PACK_STORE=0``).
 """
 import os
 import statistics
@@ -35,7 +42,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from vit_ae_plus_plus_amd.model.vit import VisionTransformer3D                                      # noqa: E402
-from vit_ae_plus_plus_amd.other_baselines.mocov3.moco.builder import MoCo_ViT                        # noqa: E402
+from vit_ae_plus_plus_amd.other_baselines.mocov3.moco.builder import MoCo_ResNet, MoCo_ViT           # noqa: E402
 from vit_ae_plus_plus_amd.other_baselines.mocov3.moco.optimizer import LARS                          # noqa: E402
 
 ROUTES = {'bf16': dict(precision='bf16'), 'act16': dict(precision='bf16', activations='bf16')}
@@ -100,8 +107,12 @@ def windows(fns, reps, inner):
 
 
 def make(route, depth, kernels):
-    enc = partial(VisionTransformer3D, in_chans=4, volume_size=96, depth=depth, **ROUTES[route])
-    model = MoCo_ViT(enc, 256, 4096, 0.2).cuda().train()
+    if route == 'resnet':
+        from vit_ae_plus_plus_amd.other_baselines.mocov3.moco.resent3d_base import generate_model
+        model = MoCo_ResNet(partial(generate_model, model_depth=10, n_input_channels=4), 256, 4096, 0.2).cuda().train()
+    else:
+        enc = partial(VisionTransformer3D, in_chans=4, volume_size=96, depth=depth, **ROUTES[route])
+        model = MoCo_ViT(enc, 256, 4096, 0.2).cuda().train()
     if not kernels:
         model._update_momentum_encoder = lambda m, model=model: torch_ema(model, m)
     opt = (LARS if kernels else TorchLARS)(model.parameters(), **HP)
@@ -120,12 +131,45 @@ def step_fn(model, opt, scaler, x1, x2):
     return f
 
 
-def under(switch, fn):
-    """fn with VITAE_WEIGHT_SHADOW = switch (the updaters read it at call time)"""
+def under(switch, fn, name='VITAE_WEIGHT_SHADOW'):
+    """fn with VITAE_WEIGHT_SHADOW (or another switch read at call time) = switch"""
     def f():
-        os.environ['VITAE_WEIGHT_SHADOW'] = switch
+        os.environ[name] = switch
         fn()
     return f
+
+
+def resnet_main(batches, reps, inner):
+    fmt = lambda t: f'{t[0]:.3f} ({t[1]:.3f} .. {t[2]:.3f})'
+    rows = []
+    print('| MoCo_ResNet, ResNet-10 | batch / view | kernels ms (min .. max) | torch statements ms (min .. max) | ratio |')
+    print('|---|---|---|---|---|')
+    for B in batches:
+        g = torch.Generator().manual_seed(B)
+        x1 = torch.randn(B, 4, 96, 96, 96, generator=g).cuda()
+        x2 = torch.randn(B, 4, 96, 96, 96, generator=g).cuda()
+        a, b = make('resnet', 0, True), make('resnet', 0, False)
+        fa, fb = step_fn(*a, x1, x2), step_fn(*b, x1, x2)
+        for _ in range(3):
+            fa(); fb()
+        ka, tb = windows([fa, fb], reps, inner)
+        print(f'| step | {B} | {fmt(ka)} | {fmt(tb)} | {tb[0] / ka[0]:.3f} |', flush=True)
+        del b, fb
+        torch.cuda.empty_cache()
+        c = make('resnet', 0, True)
+        f0, f1 = under('0', fa, 'VITAE_CONV_PACK_STORE'), under('1', step_fn(*c, x1, x2), 'VITAE_CONV_PACK_STORE')
+        for _ in range(3):
+            f0(); f1()
+        off, on = windows([f0, f1], reps, inner)
+        os.environ.pop('VITAE_CONV_PACK_STORE', None)
+        rows.append(f'| step | {B} | {fmt(off)} | {fmt(on)} | {on[0] / off[0]:.4f} | {off[2] - off[1]:.3f} |')
+        del a, c, fa, f0, f1
+        torch.cuda.empty_cache()
+    print()
+    print('| MoCo_ResNet, ResNet-10 | batch / view | a pack per call ms (min .. max) | operand store ms (min .. max) | store / per call | spread of per call ms |')
+    print('|---|---|---|---|---|---|')
+    for row in rows:
+        print(row)
 
 
 def shadow_main(batches, routes, reps, inner, depth):
@@ -174,6 +218,8 @@ def main():
     routes = _option('routes', 'act16' if _option('shadow', '') else 'bf16,act16').split(',')
     reps, inner, depth = int(_option('reps', '9')), int(_option('inner', '5')), int(_option('depth', '12'))
     print(f'# device {torch.cuda.get_device_name(0)}; reps {reps} x {inner} steps per window; depth {depth}')
+    if _option('arch', 'vit') == 'resnet':
+        return resnet_main(batches, reps, inner)
     if _option('shadow', ''):
         if _option('shadow', '') != '0,1':
             sys.exit("moco_bench.py: shadow takes '0,1'")

@@ -5,6 +5,11 @@ routes timed in turns A, B, A, B ... inside this process, each timed call betwee
 route; then a per-kernel table of one HIP step (every launch sequence of vit_ae_plus_plus_amd.resnet between two synchronisations).
 
     python tools/resnet_bench.py [step] [kernels] [--batch B] [--iters N]        (no argument: both rows, batch 4 and 16)
+    python tools/resnet_bench.py pack [--batch B] [--iters N]
+
+``pack``: the HIP step with the per-model operand store (``resnet.ConvPackStore``: every stale convolution operand in one
+``vitae_conv3d_pack_weights_multi`` launch per step) against a pack per convolution call (``VITAE_CONV_PACK_STORE=0``), two models
+alternating in this process.
 """
 import collections
 import os
@@ -137,6 +142,28 @@ def step_rows(B):
           f'{kept_mib(kept):.0f} MiB for the backward', flush=True)
 
 
+def pack_rows(B):
+    x = torch.randn(B, CHANNELS, VOLUME, VOLUME, VOLUME, device='cuda')
+    y = torch.randint(0, 2, (B,), device='cuda')
+    crit = nn.CrossEntropyLoss(weight=torch.tensor([3.0, 1.0], device='cuda'))
+    models = [generate_model(10, n_classes=2, n_input_channels=CHANNELS).cuda().train() for _ in range(2)]
+    opts = [torch.optim.Adam(m.parameters(), lr=1e-4) for m in models]
+
+    def step(i, switch):
+        def f():
+            os.environ['VITAE_CONV_PACK_STORE'] = switch
+            opts[i].zero_grad(set_to_none=True)
+            crit(models[i](x), y).backward()
+            opts[i].step()
+        return f
+
+    off, on = timed_ab(step(0, '0'), step(1, '1'))
+    os.environ.pop('VITAE_CONV_PACK_STORE', None)
+    fmt = lambda t: f'{t[0]:.3f} ms ({t[1]:.3f} .. {t[2]:.3f})'
+    print(f'resnet10 B={B} step with Adam: a pack per call {fmt(off)}, operand store {fmt(on)}, store / per call = {on[0] / off[0]:.4f}; '
+          f'{seq.pack_store_of(models[1]).launches} pack launches in {ITERS + WARMUP} steps', flush=True)
+
+
 def kernel_rows(B):
     """One HIP step with every launch sequence of vit_ae_plus_plus_amd.resnet timed on its own (synchronised before and after)."""
     table = collections.OrderedDict()
@@ -185,4 +212,6 @@ for B in ([BATCH] if BATCH else [4, 16]):
         step_rows(B)
     if 'kernels' in ROWS:
         kernel_rows(B)
+    if 'pack' in ROWS:
+        pack_rows(B)
     torch.cuda.empty_cache()

@@ -82,6 +82,62 @@ __global__ __launch_bounds__(256) void conv3d_pack_kernel(const float* __restric
     out[i] = (__bf16)v;
 }
 
+// Every operand of a network in one launch: the destinations laid end to end and cut into chunks of PACK_CHUNK elements; chunks[2 c],
+// chunks[2 c + 1] = the entry in which chunk c begins and the offset there in groups of 8.  A thread converts 8 consecutive k of one
+// row (a packed size is a multiple of 16, so a group lies in one row of one entry) with conv3d_pack_kernel's expression per element
+// and stores them as 16 bytes; it walks on to the next entry when its group lies behind the current one.
+static_assert(VITAE_CONV3D_PACK_CHUNK % (8 * 256) == 0, "a chunk is a whole number of groups per thread");
+struct PackEntry { const float* w; __bf16* out; long long Cout, Cin, kd, kh, kw, transposed; };
+constexpr int PACK_GROUPS = VITAE_CONV3D_PACK_CHUNK / 8;
+
+__host__ __device__ inline long pack_entry_groups(const PackEntry& e, int& taps, int& Kp) {
+    taps = (int)(e.kd * e.kh * e.kw);
+    const long K = (long)taps * (e.transposed ? e.Cout : e.Cin);
+    Kp = (int)((K + KSTEP - 1) / KSTEP * KSTEP);
+    return (e.transposed ? e.Cin : e.Cout) * (long)Kp / 8;
+}
+
+__global__ __launch_bounds__(256) void conv3d_pack_multi_kernel(const PackEntry* __restrict__ table, int n_entries, const int* __restrict__ chunks,
+                                                                long total_groups) {
+    const long first = (long)blockIdx.x * PACK_GROUPS;
+    const int n = (int)(total_groups - first < PACK_GROUPS ? total_groups - first : PACK_GROUPS);
+    int t = chunks[2 * blockIdx.x];
+    long start = -(long)chunks[2 * blockIdx.x + 1];       // the chunk-local group at which entry t begins
+    PackEntry e = table[t];
+    int taps, Kp;
+    long groups = pack_entry_groups(e, taps, Kp);
+    // Slot j of the chunk is group (j % 16) * (PACK_GROUPS / 16) + j / 16: 16 neighbouring lanes take groups 256 elements apart — for
+    // the wide layers one tap apart, neighbouring source addresses — and lanes l, l + 16, l + 32, l + 48 neighbouring groups (64
+    // bytes of one destination line).  A thread's groups still ascend, so it only ever walks forward through the table.
+    for (int j = threadIdx.x; j < PACK_GROUPS; j += 256) {
+        const int i = (j & 15) * (PACK_GROUPS / 16) + (j >> 4);
+        if (i >= n) continue;
+        while (i - start >= groups) {
+            start += groups;
+            if (++t >= n_entries) return;                 // (the launcher checked the list: not reached)
+            e = table[t];
+            groups = pack_entry_groups(e, taps, Kp);
+        }
+        const long o = (i - start) * 8;
+        const int row = (int)(o / Kp), k0 = (int)(o % Kp);
+        const int Cout = (int)e.Cout, Cin = (int)e.Cin;
+        const int inner = e.transposed ? Cout : Cin;      // k = tap * inner + c
+        bf16x8 h;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = k0 + j;
+            float v = 0.f;
+            if (k < taps * inner) {
+                const int tap = k / inner, c = k % inner;
+                const int co = e.transposed ? c : row, ci = e.transposed ? row : c;
+                v = e.w[((long)co * Cin + ci) * taps + tap];
+            }
+            h[j] = (__bf16)v;
+        }
+        *reinterpret_cast<bf16x8*>(e.out + o) = h;
+    }
+}
+
 __global__ __launch_bounds__(256) void channels_last_bf16_kernel(const float* __restrict__ x, __bf16* __restrict__ out, int C, long S, long total) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;      // output index: (n S + s) C + c
     if (i >= total) return;
@@ -396,6 +452,75 @@ extern "C" int vitae_conv3d_pack_weight(const float* w, void* w16, int Cout, int
     const long total = (long)(transposed ? Cin : Cout) * Kp;
     hipLaunchKernelGGL(conv3d_pack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, reinterpret_cast<__bf16*>(w16), Cout, Cin,
                        taps, (int)Kp, transposed ? 1 : 0, total);
+    return vitae_launch_status();
+}
+
+namespace {
+// VITAE_OK or the refusal of a pack table (host copy); total_groups: all destinations in groups of 8 elements
+int pack_multi_check(const long long* table, long n_entries, long& total_groups) {
+    if (!table || n_entries <= 0 || n_entries > INT_MAX) return VITAE_ERR_INVALID_ARG;
+    total_groups = 0;
+    for (long t = 0; t < n_entries; ++t) {
+        const long long* w = table + t * VITAE_CONV3D_PACK_ENTRY_WORDS;
+        const long long Cout = w[2], Cin = w[3], kd = w[4], kh = w[5], kw = w[6], tr = w[7];
+        if (!w[0] || !w[1] || Cout <= 0 || Cin <= 0 || Cout > INT_MAX || Cin > INT_MAX || (tr != 0 && tr != 1)) return VITAE_ERR_INVALID_ARG;
+        if (kd < 1 || kh < 1 || kw < 1 || kd > 7 || kh > 7 || kw > 7 || (Cout & 3)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+        if (w[1] & 15) return VITAE_ERR_UNSUPPORTED_SHAPE;
+        if (kpad(kd * kh * kw * (tr ? Cout : Cin)) > (long)INT_MAX - 256) return VITAE_ERR_UNSUPPORTED_SHAPE;
+        const long elems = vitae_conv3d_packed_elems((int)Cout, (int)Cin, (int)kd, (int)kh, (int)kw, (int)tr);
+        if (elems <= 0 || elems > VITAE_CONV3D_PACK_MAX_ELEMS) return VITAE_ERR_UNSUPPORTED_SHAPE;
+        total_groups += elems / 8;
+        if (total_groups * 8 > VITAE_CONV3D_PACK_MAX_ELEMS) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    }
+    return VITAE_OK;
+}
+
+// the chunk list of a checked table: written to `out` (check == NULL) or compared with `check`
+bool pack_multi_walk(const long long* table, long n_entries, long n_chunks, int* out, const int* check) {
+    const auto groups_of = [&](long t) {
+        const long long* w = table + t * VITAE_CONV3D_PACK_ENTRY_WORDS;
+        return vitae_conv3d_packed_elems((int)w[2], (int)w[3], (int)w[4], (int)w[5], (int)w[6], (int)w[7]) / 8;
+    };
+    long t = 0, off = 0, groups = groups_of(0);           // where the next chunk begins: entry, group offset inside it
+    for (long c = 0; c < n_chunks; ++c) {
+        if (t >= n_entries) return false;
+        if (check) { if (check[2 * c] != (int)t || check[2 * c + 1] != (int)off) return false; }
+        else { out[2 * c] = (int)t; out[2 * c + 1] = (int)off; }
+        long left = PACK_GROUPS;
+        while (left > 0 && t < n_entries) {
+            const long take = groups - off < left ? groups - off : left;
+            off += take; left -= take;
+            if (off == groups) {
+                off = 0;
+                if (++t < n_entries) groups = groups_of(t);
+            }
+        }
+    }
+    return t == n_entries;                                // the list covers every entry, no more
+}
+}  // namespace
+
+extern "C" long vitae_conv3d_pack_multi_chunks(const long long* table_host, long n_entries) {
+    long total_groups;
+    if (pack_multi_check(table_host, n_entries, total_groups) != VITAE_OK) return 0;
+    return cdiv(total_groups, (long)PACK_GROUPS);
+}
+
+extern "C" int vitae_conv3d_pack_multi_chunk_list(const long long* table_host, long n_entries, int* chunks_host, long n_chunks) {
+    long total_groups;
+    if (const int rc = pack_multi_check(table_host, n_entries, total_groups)) return rc;
+    if (!chunks_host || n_chunks != cdiv(total_groups, (long)PACK_GROUPS)) return VITAE_ERR_INVALID_ARG;
+    return pack_multi_walk(table_host, n_entries, n_chunks, chunks_host, nullptr) ? VITAE_OK : VITAE_ERR_INVALID_ARG;
+}
+
+extern "C" int vitae_conv3d_pack_weights_multi(const long long* table_host, const long long* table_dev, long n_entries, const int* chunks_host,
+                                               const int* chunks_dev, long n_chunks, void* stream) {
+    long total_groups;
+    if (const int rc = pack_multi_check(table_host, n_entries, total_groups)) return rc;
+    if (!table_dev || !chunks_host || !chunks_dev || n_chunks != cdiv(total_groups, (long)PACK_GROUPS)) return VITAE_ERR_INVALID_ARG;
+    if (!pack_multi_walk(table_host, n_entries, n_chunks, nullptr, chunks_host)) return VITAE_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(conv3d_pack_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const PackEntry*>(table_dev), (int)n_entries, chunks_dev, total_groups);
     return vitae_launch_status();
 }
 

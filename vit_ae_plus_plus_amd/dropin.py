@@ -36,6 +36,8 @@ _ALIASES = {
     'other_baselines.mocov3.moco.optimizer': 'vit_ae_plus_plus_amd.other_baselines.mocov3.moco.optimizer',
     # (the baseline's own copy of the encoder is model/vit.py without the contrastive class)
     'other_baselines.mocov3.moco.vit_3d': 'vit_ae_plus_plus_amd.model.vit',
+    # its copy of the 3-D ResNet (keyword num_classes): the backbone of MoCo_ResNet, the script's default --arch
+    'other_baselines.mocov3.moco.resent3d_base': 'vit_ae_plus_plus_amd.other_baselines.mocov3.moco.resent3d_base',
     # the supervised 3-D ResNet baseline; the pre-training scripts import get_all_feat_and_labels from train_3d_resnet
     'k_fold_training_scripts': 'vit_ae_plus_plus_amd.k_fold_training_scripts',
     'k_fold_training_scripts.resnet_3d': 'vit_ae_plus_plus_amd.k_fold_training_scripts.resnet_3d',

@@ -7,8 +7,10 @@ convolutions, 1 / 0 for BatchNorm), so checkpoints interchange.  Parameters are 
 
 The sub-modules only HOLD parameters and buffers: the arithmetic runs in ``ResNet.forward`` through ``vit_ae_plus_plus_amd.resnet``
 (one autograd node for the body, one for the head in ``train()`` mode with gradients enabled; inference on the running statistics in
-``eval()`` mode or under ``no_grad``).  Calling a sub-module on its own raises ``VitaeError`` — there is no torch fallback.  Operands
-of the convolutions and of the head are bf16 with fp32 accumulation: the counterpart of the reference script's autocast region.
+``eval()`` mode or under ``no_grad``; ``forward_features`` is the same below ``fc``, and with ``batch_stats=True`` under ``no_grad`` the
+training arithmetic with nothing kept: a MoCo momentum encoder).  Calling a sub-module on its own raises ``VitaeError`` — there is no
+torch fallback.  Operands of the convolutions and of the head are bf16 with fp32 accumulation: the counterpart of the reference
+script's autocast region.
 
 Served: depths 10 / 18 / 34 (BasicBlock), shortcut 'B', any ``widen_factor`` whose widths stay multiples of 4.
 Refused at construction (``NotImplementedError``): depths 50 - 200 (Bottleneck) and shortcut 'A'.
@@ -139,15 +141,32 @@ class ResNet(nn.Module):
         layers += [block(self.in_planes, planes) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
-    def forward(self, x):
+    def forward_features(self, x, *, batch_stats=None):
+        """Everything below ``fc``: the pooled features ``[N, C]``.
+
+        ``batch_stats=None``: the rule of ``forward`` — the body's autograd node in ``train()`` mode with gradients enabled, inference on
+        the running statistics otherwise.  ``batch_stats=True`` (``train()`` mode under ``torch.no_grad()`` only, ``VitaeError`` otherwise):
+        BatchNorm on batch statistics with the running statistics and ``num_batches_tracked`` updated, nothing kept for a backward —
+        what a MoCo momentum encoder computes."""
         runner = HipResNetRunner(self)
-        prec = CONSTS['VITAE_PREC_BF16']
+        if batch_stats:
+            if torch.is_grad_enabled() or not self.training:
+                raise VitaeError('ResNet.forward_features(batch_stats=True) keeps nothing for a backward and updates the running statistics: '
+                                 'call it in train() mode under torch.no_grad()')
+            return runner.forward_batch_stats(x)
         if self.training and torch.is_grad_enabled():
             body = [(n, p) for n, p in self.named_parameters() if not n.startswith('fc.')]
-            feat = _BodyFunction.apply(runner, tuple(n for n, _ in body), x, *(p for _, p in body))
+            return _BodyFunction.apply(runner, tuple(n for n, _ in body), x, *(p for _, p in body))
+        with torch.no_grad():
+            return runner.infer(x)
+
+    def forward(self, x):
+        prec = CONSTS['VITAE_PREC_BF16']
+        feat = self.forward_features(x)
+        if self.training and torch.is_grad_enabled():
             return _HeadFunction.apply(feat, self.fc.weight, self.fc.bias, prec)
         with torch.no_grad():
-            return hip_linear(runner.infer(x), self.fc.weight, self.fc.bias, precision=prec)
+            return hip_linear(feat, self.fc.weight, self.fc.bias, precision=prec)
 
 
 def generate_model(model_depth, **kwargs):

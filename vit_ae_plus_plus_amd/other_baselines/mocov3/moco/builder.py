@@ -1,16 +1,19 @@
-"""MoCo v3 around ``VisionTransformer3D`` (reference other_baselines/mocov3/moco/builder.py; Chen, Xie, He: "An Empirical Study of
-Training Self-Supervised Vision Transformers", 2021): a base encoder and a momentum encoder with projector MLPs, a predictor MLP, the
+"""MoCo v3 around ``VisionTransformer3D`` and around the 3-D ResNet (reference other_baselines/mocov3/moco/builder.py; Chen, Xie, He:
+"An Empirical Study of Training Self-Supervised Vision Transformers", 2021): a base encoder and a momentum encoder with projector MLPs, a predictor MLP, the
 symmetrised InfoNCE loss.  Names, signatures and state-dict keys are the reference's; the arithmetic runs on libvitae_hip.so:
 
-  * the encoders go through ``forward_features`` once per step and encoder on the stacked views (trainer route for the base encoder,
-    inference route for the momentum encoder);
+  * ``MoCo_ViT``: the encoders go through ``forward_features`` once per step and encoder on the stacked views (trainer route for the
+    base encoder, inference route for the momentum encoder);
+  * ``MoCo_ResNet``: the two views go through the ResNet's launch sequence one after the other, so that every BatchNorm3d sees one
+    view's batch statistics and its running statistics move twice per step, first view first — the body's autograd node once per view
+    for the base encoder, ``forward_features(batch_stats=True)`` (batch statistics, nothing kept) for the momentum encoder;
   * the MLPs are autograd nodes over ``vitae_linear_*`` (no bias), ``vitae_bn1d_relu_*`` and ``vitae_bn1d_*``, one view at a time, so
     BatchNorm statistics are per view and running statistics move twice per step, first view first;
   * ``_update_momentum_encoder`` is ``vitae_ema_multi`` (one launch for all parameters), ``contrastive_loss`` / the loss of ``forward`` is
     ``vitae_moco_loss`` (three launches, both terms and their gradients).
 
-There is no CPU fallback: a CPU input raises ``VitaeError``.  Not built: ``MoCo_ResNet`` (no 3-D ResNet in this package),
-``concat_all_gather`` / several GPUs, SyncBatchNorm.
+There is no CPU fallback: a CPU input raises ``VitaeError``.  Not built: ``concat_all_gather`` / several GPUs, SyncBatchNorm, the
+Bottleneck depths of the ResNet (50 - 200).
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from ...._abi import VitaeError, lib
+from ....k_fold_training_scripts.resnet_3d import ResNet as _PackageResNet
 from ....model.vit import _stream, hip_linear
 from ....shadow import mark_current, shadow_column
 from .optimizer import TableRing, ema_table, fp32_on_device
@@ -181,12 +185,19 @@ class MoCo(nn.Module):
         super().__init__()
         self.T = T
         for name in ('base_encoder', 'momentum_encoder'):
-            setattr(self, name, base_encoder(num_classes=mlp_dim))
+            setattr(self, name, self._checked_encoder(base_encoder(num_classes=mlp_dim)))
         self._build_projector_and_predictor_mlps(dim, mlp_dim)
         # the momentum encoder starts as the base encoder, projector included, and is never stepped by an optimiser
         self.momentum_encoder.load_state_dict(self.base_encoder.state_dict())
         self.momentum_encoder.requires_grad_(False)
         self._ema_ring = TableRing()
+        self._configure_encoders()
+
+    def _checked_encoder(self, encoder):
+        """What ``base_encoder(...)`` returned, or the subclass's refusal of it (before anything is attached or replaced)."""
+        return encoder
+
+    def _configure_encoders(self):
         # LayerNorm parameter gradients (encoder._Trainer._ln_bwd) and, on the fp32-activation routes, Linear bias gradients (_colsum)
         # of the trained encoder without atomics: sums that cancel reproduce from run to run, and a loss scaled by a power of two
         # (GradScaler) gives the unscaled run's gradients.  (An embedding size those forms do not serve raises in the backward.)
@@ -250,9 +261,20 @@ class MoCo(nn.Module):
         # gradients sum to twice this one's: halving both is exact
         return _MocoLoss.apply(q, k, q, k, self.T) * 0.5
 
-    def _heads(self, encoder, f, B):
+    def _views(self, x1, x2):
+        """What ``_features`` takes: here the stacked views, one encoder call for both (the encoder has no batch statistics)."""
+        return torch.cat([x1, x2], dim=0)
+
+    def _features(self, encoder, views, momentum):
+        """-> the encoder's features of the first and of the second view.  ``momentum``: this is the momentum encoder, under no_grad."""
+        f = encoder.forward_features(views)
+        B = f.shape[0] // 2
+        return f[:B], f[B:]
+
+    def _heads(self, encoder, f1, f2):
         """The projector of ``encoder`` on each view's features, first view first."""
-        return run_mlp(encoder.head, f[:B]), run_mlp(encoder.head, f[B:])
+        mlp = getattr(encoder, self.PROJECTOR_ATTR)
+        return run_mlp(mlp, f1), run_mlp(mlp, f2)
 
     def forward(self, x1, x2, m):
         """x1, x2: the two views [B, C, L, H, W]; m: momentum of the update.  -> the loss (0-dim; differentiable in training mode)."""
@@ -261,22 +283,49 @@ class MoCo(nn.Module):
                 raise VitaeError(f'MoCo.forward: input is on {x.device}; this package computes on MI355X only (no CPU fallback)')
         if x1.shape != x2.shape:
             raise VitaeError('MoCo.forward: the two views must have one shape')
-        B = x1.shape[0]
-        x = torch.cat([x1, x2], dim=0)
-        # one encoder call on the stacked views (the encoder has no batch statistics); heads and predictor per view
+        x = self._views(x1, x2)
+        # the encoder as the subclass runs it (_features); heads and predictor per view
         # (eval() mode is inference, as for VisionTransformer3D: running statistics normalise, nothing is differentiated)
         with torch.set_grad_enabled(torch.is_grad_enabled() and self.training):
-            p1, p2 = self._heads(self.base_encoder, self.base_encoder.forward_features(x), B)
+            p1, p2 = self._heads(self.base_encoder, *self._features(self.base_encoder, x, False))
             q1, q2 = run_mlp(self.predictor, p1), run_mlp(self.predictor, p2)
         with torch.no_grad():
             self._update_momentum_encoder(m)
-            k1, k2 = self._heads(self.momentum_encoder, self.momentum_encoder.forward_features(x), B)
+            k1, k2 = self._heads(self.momentum_encoder, *self._features(self.momentum_encoder, x, True))
         return _MocoLoss.apply(q1, k2, q2, k1, self.T)
 
 
 class MoCo_ResNet(MoCo):
-    def __init__(self, *a, **k):
-        raise NotImplementedError('MoCo_ResNet: the 3-D ResNet backbone is not part of this package; MoCo_ViT wraps VisionTransformer3D')
+    """MoCo v3 over this package's 3-D ResNet (``resent3d_base.generate_model`` / ``k_fold_training_scripts.resnet_3d``; depths 10 / 18
+    / 34): a 2-layer projector in place of each encoder's ``fc``, a 2-layer predictor without a last BatchNorm.  ``base_encoder``: a
+    callable taking ``num_classes=``, in practice ``partial(generate_model, model_depth=10, n_input_channels=...)``; one that returns
+    anything but this package's ``ResNet`` is refused with ``NotImplementedError``."""
+    PROJECTOR_ATTR = 'fc'
+
+    def _checked_encoder(self, encoder):
+        if not isinstance(encoder, _PackageResNet):
+            raise NotImplementedError(f'MoCo_ResNet wraps only the 3-D ResNet of this package (resent3d_base.generate_model, depths 10 / 18 / '
+                                      f'34), not {type(encoder).__module__}.{type(encoder).__qualname__}; MoCo_ViT wraps VisionTransformer3D')
+        return encoder
+
+    def _configure_encoders(self):
+        pass                # the ResNet's backward has no atomics: nothing to switch
+
+    def _build_projector_and_predictor_mlps(self, dim, mlp_dim):
+        hidden_dim = self.base_encoder.fc.weight.shape[1]
+        del self.base_encoder.fc, self.momentum_encoder.fc              # the classifiers
+        self.base_encoder.fc = self._build_mlp(2, hidden_dim, mlp_dim, dim)
+        self.momentum_encoder.fc = self._build_mlp(2, hidden_dim, mlp_dim, dim)
+        self.predictor = self._build_mlp(2, dim, mlp_dim, dim, False)
+
+    def _views(self, x1, x2):
+        return x1, x2
+
+    def _features(self, encoder, views, momentum):
+        # one launch sequence per view, first view first: per-view batch statistics, running statistics moved twice.  The momentum
+        # encoder stays in train() mode under no_grad in the reference: batch statistics there too (eval(): the running ones)
+        batch_stats = True if momentum and encoder.training else None
+        return tuple(encoder.forward_features(x, batch_stats=batch_stats) for x in views)
 
 
 class MoCo_ViT(MoCo):

@@ -12,10 +12,18 @@ BatchNorm reads (the convolution's output) and what a residual adds are fp32.  L
 Kept per block for the backward: the bf16 input of each convolution, the fp32 output of each convolution (what BatchNorm
 normalises), the fp32 outputs of the two ReLUs (their masks; the block output is also the next block's residual), mean / rstd.
 Nothing here falls back to torch operators: a missing kernel is an error.
+
+The bf16 operands of the convolutions live in a per-model ``ConvPackStore``: all stale ones are re-packed by one
+``vitae_conv3d_pack_weights_multi`` launch when the first of them is asked for.  ``forward_batch_stats`` is the training arithmetic with
+nothing kept (a MoCo momentum encoder).
 """
+import os
+import weakref
+
+import numpy as np
 import torch
 
-from ._abi import VitaeError, lib
+from ._abi import CONSTS, VitaeError, lib
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -42,7 +50,12 @@ def conv_out_vol(vol, conv):
     return tuple((vol[i] + 2 * conv.padding[i] - conv.kernel_size[i]) // conv.stride[i] + 1 for i in range(3))
 
 
-def pack_weight(conv, transposed):
+def pack_weight(conv, transposed, packs=None):
+    """The bf16 operand of ``conv`` (``transposed``: the input gradient's form).  ``packs``: the model's ``ConvPackStore`` — the stored
+    operand, refreshed with every other stale one of the model in one launch; without it (or with ``VITAE_CONV_PACK_STORE=0``) a new
+    buffer and one ``vitae_conv3d_pack_weight`` launch per call.  The same bits either way."""
+    if packs is not None and pack_store_enabled():
+        return packs.operand(conv, transposed)
     w = _param(conv.weight, 'a convolution weight')
     n = lib.vitae_conv3d_packed_elems(conv.out_channels, conv.in_channels, *conv.kernel_size, transposed)
     out = torch.empty(n, dtype=BF16, device=w.device)
@@ -50,18 +63,133 @@ def pack_weight(conv, transposed):
     return out
 
 
-def conv_fwd(x16, N, vol, conv):
+def pack_store_enabled():
+    """``VITAE_CONV_PACK_STORE`` (default on; read at call time): 0 packs per call, for A/B runs and the equality test."""
+    return os.environ.get('VITAE_CONV_PACK_STORE', '1') != '0'
+
+
+class ConvPackStore:
+    """Persistent bf16 operands of every convolution of one ResNet, in every form its routes use (forward and transposed; the stem,
+    whose input has no gradient, forward only) — the analogue of ``shadow.ShadowStore`` for packed convolution weights.
+
+    An operand records the weight state it was packed from, ``(data_ptr, _version)``, and is current while that still matches.  ``operand()`` returns a current one as it is; otherwise ALL stale operands of the model are re-packed by one
+    ``vitae_conv3d_pack_weights_multi`` launch.  Whatever writes a weight bumps its version: torch optimisers, ``load_state_dict`` and
+    in-place edits by themselves, the raw-pointer updaters (EMA, LARS, MultiTensorAdamW) through ``increment_version``.  The table and
+    its chunk list live in one pinned buffer with a device copy; both are rebuilt only when an address or the stale set changes.
+    ``launches`` / ``table_builds`` count for the tests."""
+
+    def __init__(self, model):
+        self.model = weakref.ref(model)
+        self.launches = 0
+        self.table_builds = 0
+        self._entries = None        # [dict(conv, transposed, geo, data, key)], the forms of one convolution next to each other
+        self._index = {}            # (id(conv), transposed) -> entry
+        self._table = None          # dict(sig, pinned, dev, n, chunks, keep)
+
+    def __reduce__(self):           # a pickled or deep-copied model carries no store along: the copy makes its own
+        return (_no_store, ())
+
+    def _enumerate(self):
+        model = self.model()
+        stem = getattr(model, 'conv1', None)
+        self._entries, self._index, self._table = [], {}, None
+        for conv in model.modules():
+            if isinstance(conv, torch.nn.Conv3d):
+                for transposed in ((0,) if conv is stem else (0, 1)):
+                    e = dict(conv=conv, transposed=transposed, data=None, key=None,
+                             geo=(conv.out_channels, conv.in_channels, *conv.kernel_size, transposed))
+                    self._entries.append(e)
+                    self._index[(id(conv), transposed)] = e
+
+    @staticmethod
+    def _key(conv):
+        w = conv._parameters['weight']
+        return (w.data_ptr(), w._version)
+
+    def operand(self, conv, transposed):
+        e = self._index.get((id(conv), int(transposed)))
+        if e is None or e['conv'] is not conv:
+            self._enumerate()
+            e = self._index.get((id(conv), int(transposed)))
+            if e is None:
+                raise VitaeError('ConvPackStore: this convolution (in this form) is not part of the model the store belongs to')
+        if e['key'] != self._key(conv):
+            self._refresh()
+        return e['data']
+
+    def _refresh(self):
+        stale, sig, last, key = [], [], None, None
+        for i, e in enumerate(self._entries):
+            if e['conv'] is not last:
+                last, key = e['conv'], self._key(e['conv'])
+            if e['key'] != key:
+                stale.append((e, key))
+                sig.append((i, key[0]))
+        t = self._table
+        if t is None or t['sig'] != sig:       # another stale set, or a weight that moved: judge the weights again, make a new table
+            t = self._table = self._build_table(stale, sig)
+        with torch.cuda.device(t['dev'].device):
+            lib.vitae_conv3d_pack_weights_multi(t['th'], t['td'], t['n'], t['ch'], t['cd'], t['chunks'], torch.cuda.current_stream().cuda_stream)
+        self.launches += 1
+        for e, key in stale:
+            e['key'] = key
+
+    def _build_table(self, stale, sig):
+        weights = [_param(e['conv'].weight, 'a convolution weight') for e, _ in stale]
+        device = weights[0].device
+        rows = []
+        for (e, _), w in zip(stale, weights):
+            if w.device != device:
+                raise VitaeError('ConvPackStore: the convolutions of one model must be on one device')
+            if tuple(w.shape) != (*e['geo'][:2], *e['geo'][2:5]):
+                raise VitaeError(f'ConvPackStore: a weight of shape {tuple(w.shape)} in a convolution of geometry {e["geo"][:5]}')
+            n = lib.vitae_conv3d_packed_elems(*e['geo'])
+            if e['data'] is None or e['data'].numel() != n or e['data'].device != device:
+                e['data'] = torch.empty(n, dtype=BF16, device=device)
+            rows.append((w.data_ptr(), e['data'].data_ptr(), *e['geo']))
+        n, ew = len(rows), CONSTS['VITAE_CONV3D_PACK_ENTRY_WORDS']
+        table = np.array(rows, dtype=np.int64).reshape(n, ew)
+        chunks = int(lib.vitae_conv3d_pack_multi_chunks(table.ctypes.data, n))
+        if chunks <= 0:
+            raise VitaeError('vitae_conv3d_pack_weights_multi refuses this set of convolutions (geometry, alignment or total size)')
+        # fresh buffers each time (a launch already enqueued may still read the old ones); [table | chunk list (int32 pairs)]
+        pinned = torch.empty(n * ew + chunks, dtype=torch.int64, pin_memory=True)
+        pinned.numpy()[:n * ew] = table.reshape(-1)
+        th = pinned.data_ptr()
+        lib.vitae_conv3d_pack_multi_chunk_list(th, n, th + 8 * n * ew, chunks)
+        dev = torch.empty(n * ew + chunks, dtype=torch.int64, device=device)
+        dev.copy_(pinned, non_blocking=True)
+        td = dev.data_ptr()
+        self.table_builds += 1
+        # a weight that had to be copied to be contiguous lives in `weights` only: such a table is never found again (sig None)
+        copied = any(w.data_ptr() != key[0] for (_, key), w in zip(stale, weights))
+        return dict(sig=None if copied else sig, pinned=pinned, dev=dev, n=n, chunks=chunks, th=th, td=td, ch=th + 8 * n * ew, cd=td + 8 * n * ew)
+
+
+def _no_store():
+    return None
+
+
+def pack_store_of(model):
+    """The ``ConvPackStore`` of ``model`` (a ResNet), made on first use."""
+    st = model.__dict__.get('_conv_packs')
+    if st is None or st.model() is not model:
+        st = model.__dict__['_conv_packs'] = ConvPackStore(model)
+    return st
+
+
+def conv_fwd(x16, N, vol, conv, packs=None):
     """-> fp32 [M, Cout], output volume"""
     ovol = conv_out_vol(vol, conv)
     y = torch.empty(N * ovol[0] * ovol[1] * ovol[2], conv.out_channels, dtype=F32, device=x16.device)
-    lib.vitae_conv3d_fwd(x16.data_ptr(), pack_weight(conv, 0).data_ptr(), y.data_ptr(), None, *_geo(N, vol, conv), _st(x16))
+    lib.vitae_conv3d_fwd(x16.data_ptr(), pack_weight(conv, 0, packs).data_ptr(), y.data_ptr(), None, *_geo(N, vol, conv), _st(x16))
     return y, ovol
 
 
-def conv_bwd_input(dy16, N, vol, conv, into=None):
+def conv_bwd_input(dy16, N, vol, conv, into=None, packs=None):
     """dx fp32 [N D H W, Cin]; `into`: the sum is added to that tensor (the residual branch's gradient) instead"""
     dx = into if into is not None else torch.empty(N * vol[0] * vol[1] * vol[2], conv.in_channels, dtype=F32, device=dy16.device)
-    lib.vitae_conv3d_bwd_input(dy16.data_ptr(), pack_weight(conv, 1).data_ptr(), dx.data_ptr(), None, 0 if into is None else 1,
+    lib.vitae_conv3d_bwd_input(dy16.data_ptr(), pack_weight(conv, 1, packs).data_ptr(), dx.data_ptr(), None, 0 if into is None else 1,
                                *_geo(N, vol, conv), _st(dy16))
     return dx
 
@@ -123,6 +251,7 @@ class HipResNetRunner:
 
     def __init__(self, model):
         self.model = model
+        self.packs = pack_store_of(model)
 
     def blocks(self):
         for li in range(1, 5):
@@ -130,9 +259,13 @@ class HipResNetRunner:
                 yield f'layer{li}.{bi}', blk
 
     # ------------------------------------------------------------------ forward
-    def _forward(self, x, train):
-        """-> features fp32 [N, C] and (train) what the backward needs"""
-        m = self.model
+    def _forward(self, x, train, keep=None):
+        """-> features fp32 [N, C] and (keep; default: train) what the backward needs.  train: BatchNorm on batch statistics, the running
+        statistics updated.  Without ``keep`` no record is collected: an activation is released as soon as the sequence has passed it."""
+        m, packs = self.model, self.packs
+        keep = train if keep is None else keep
+        if keep and not train:
+            raise VitaeError('ResNet: the backward needs the batch statistics; the inference route keeps nothing')
         if not x.is_cuda:
             raise VitaeError(f'ResNet: input is on {x.device}; this package computes on MI355X only (no CPU fallback).')
         if x.dim() != 5 or x.shape[1] != m.conv1.in_channels:
@@ -140,44 +273,59 @@ class HipResNetRunner:
         bn = bn_tail_train if train else (lambda x_, res, bn_, relu, want16: bn_tail_eval(x_, res, bn_, relu, want16) + (None, None))
         x = x.detach().contiguous().float()
         N, C, vol0 = x.shape[0], x.shape[1], tuple(x.shape[2:])
-        st = _st(x)
-        x16 = torch.empty(N * vol0[0] * vol0[1] * vol0[2], C, dtype=BF16, device=x.device)
+        st, dev = _st(x), x.device
+        x16 = torch.empty(N * vol0[0] * vol0[1] * vol0[2], C, dtype=BF16, device=dev)
         lib.vitae_to_channels_last_bf16(x.data_ptr(), x16.data_ptr(), N, C, *vol0, st)
-        pre, vol = conv_fwd(x16, N, vol0, m.conv1)
+        pre, vol = conv_fwd(x16, N, vol0, m.conv1, packs=packs)
         y, y16, mean, rstd = bn(pre, None, m.bn1, 1, m.no_max_pool)
-        stem = dict(x16=x16, vol_in=vol0, pre=pre, y=y, mean=mean, rstd=rstd, vol=vol, idx=None)
+        stem = dict(x16=x16, vol_in=vol0, pre=pre, y=y, mean=mean, rstd=rstd, vol=vol, idx=None) if keep else None
         cur, cur16 = y, y16
+        del x, x16, pre, mean, rstd
         if not m.no_max_pool:
             C0 = y.shape[1]
             pvol = tuple((v - 1) // 2 + 1 for v in vol)
             rows = N * pvol[0] * pvol[1] * pvol[2]
-            cur, cur16 = torch.empty(rows, C0, dtype=F32, device=x.device), torch.empty(rows, C0, dtype=BF16, device=x.device)
-            idx = torch.empty(rows, C0, dtype=torch.uint8, device=x.device)
+            cur, cur16 = torch.empty(rows, C0, dtype=F32, device=dev), torch.empty(rows, C0, dtype=BF16, device=dev)
+            idx = torch.empty(rows, C0, dtype=torch.uint8, device=dev)
             lib.vitae_maxpool3d_fwd(y.data_ptr(), cur.data_ptr(), cur16.data_ptr(), idx.data_ptr(), N, *vol, C0, st)
-            stem['idx'], vol = idx, pvol
+            if keep:
+                stem['idx'] = idx
+            vol = pvol
+            del idx
+        del y, y16
         recs = []
         for _, blk in self.blocks():
-            pre1, ovol = conv_fwd(cur16, N, vol, blk.conv1)
+            pre1, ovol = conv_fwd(cur16, N, vol, blk.conv1, packs=packs)
             y1, y1_16, mean1, rstd1 = bn(pre1, None, blk.bn1, 1, True)
-            pre2, _ = conv_fwd(y1_16, N, ovol, blk.conv2)
+            pre2, _ = conv_fwd(y1_16, N, ovol, blk.conv2, packs=packs)
             rec = dict(in16=cur16, vol_in=vol, vol=ovol, pre1=pre1, y1=y1, y1_16=y1_16, mean1=mean1, rstd1=rstd1, pre2=pre2)
+            del pre1, y1, y1_16
             if blk.downsample is not None:
-                pred, _ = conv_fwd(cur16, N, vol, blk.downsample[0])
+                pred, _ = conv_fwd(cur16, N, vol, blk.downsample[0], packs=packs)
                 res, _, meand, rstdd = bn(pred, None, blk.downsample[1], 0, False)
                 rec.update(pred=pred, meand=meand, rstdd=rstdd)
+                del pred
             else:
                 res = cur
             cur, cur16, mean2, rstd2 = bn(pre2, res, blk.bn2, 1, True)
             rec.update(out=cur, mean2=mean2, rstd2=rstd2)
-            recs.append(rec)
+            del pre2, res
+            if keep:
+                recs.append(rec)
+            del rec
             vol = ovol
         S, Cl = vol[0] * vol[1] * vol[2], cur.shape[1]
-        feat = torch.empty(N, Cl, dtype=F32, device=x.device)
+        feat = torch.empty(N, Cl, dtype=F32, device=dev)
         lib.vitae_rows_mean_fwd(cur.data_ptr(), feat.data_ptr(), None, N, S, Cl, st)
-        return feat, (dict(N=N, S=S, stem=stem, recs=recs) if train else None)
+        return feat, (dict(N=N, S=S, stem=stem, recs=recs) if keep else None)
 
     def infer(self, x):
         return self._forward(x, False)[0]
+
+    def forward_batch_stats(self, x):
+        """The training arithmetic (batch statistics, running statistics and ``num_batches_tracked`` updated) with nothing kept: what a
+        momentum encoder in ``train()`` mode under ``no_grad`` computes."""
+        return self._forward(x, True, keep=False)[0]
 
     def forward_keep(self, x):
         return self._forward(x, True)
@@ -198,7 +346,7 @@ class HipResNetRunner:
             d2_16, grads[f'{name}.bn2.weight'], grads[f'{name}.bn2.bias'] = bn_tail_bwd(dcur, rec['pre2'], rec['out'], blk.bn2, rec['mean2'],
                                                                                       rec['rstd2'], 1, dres)
             grads[f'{name}.conv2.weight'] = conv_bwd_weight(d2_16, rec['y1_16'], N, vout, blk.conv2)
-            dy1 = conv_bwd_input(d2_16, N, vout, blk.conv2)
+            dy1 = conv_bwd_input(d2_16, N, vout, blk.conv2, packs=self.packs)
             d1_16, grads[f'{name}.bn1.weight'], grads[f'{name}.bn1.bias'] = bn_tail_bwd(dy1, rec['pre1'], rec['y1'], blk.bn1, rec['mean1'],
                                                                                       rec['rstd1'], 1)
             grads[f'{name}.conv1.weight'] = conv_bwd_weight(d1_16, rec['in16'], N, vin, blk.conv1)
@@ -208,8 +356,8 @@ class HipResNetRunner:
                 dd_16, grads[f'{name}.downsample.1.weight'], grads[f'{name}.downsample.1.bias'] = bn_tail_bwd(
                     dres, rec['pred'], None, blk.downsample[1], rec['meand'], rec['rstdd'], 0)
                 grads[f'{name}.downsample.0.weight'] = conv_bwd_weight(dd_16, rec['in16'], N, vin, blk.downsample[0])
-                din = conv_bwd_input(dd_16, N, vin, blk.downsample[0])
-            dcur = conv_bwd_input(d1_16, N, vin, blk.conv1, into=din)
+                din = conv_bwd_input(dd_16, N, vin, blk.downsample[0], packs=self.packs)
+            dcur = conv_bwd_input(d1_16, N, vin, blk.conv1, into=din, packs=self.packs)
         stem = kept['stem']
         if stem['idx'] is not None:
             dy = torch.empty_like(stem['y'])
