@@ -737,6 +737,31 @@ long vitae_conv3d_wgrad_ws_floats(int N, int D, int H, int W, int Cin, int Cout,
                                   int pd, int ph, int pw);
 int vitae_conv3d_bwd_weight(const void* dy16, const void* x16, float* dw, float* ws, long ws_floats, int accumulate, int N, int D, int H,
                             int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream);
+/* ---- fp32x3 route of the 3-D ResNet (csrc/conv3d_x3.hip; additive to ABI 57: no existing entry point changes) ----------------
+ * The same gather-GEMMs with fp32 sources and split operands.  Every fp32 value v enters the bf16 MFMA as hi = bf16(v) and
+ * lo = bf16(v - float(hi)); per k-step three v_mfma_f32_32x32x16_bf16 go into the one accumulator in this fixed order:
+ * a_lo b_hi, a_hi b_lo, a_hi b_hi (the cross terms first; lo.lo is dropped).  The row operand (x, dy) is the route's fp32
+ * channels-last tensor, split in registers by the lane that gathered it: 32 bytes per lane and k-step when its channel count is a
+ * multiple of 8, 16 bytes when a multiple of 4, element by element otherwise.  The weight is packed as two bf16 planes per row,
+ * [rows][hi (Kpad) | lo (Kpad)], k order and zero tails as above: vitae_conv3d_packed_elems_x3 = 2 x vitae_conv3d_packed_elems.
+ * Geometry, outputs, accumulate, the two-level accumulation, the chunked weight gradient (workspace of
+ * vitae_conv3d_wgrad_ws_floats floats, ordered double sum, no atomics) and the refusals are those of the bf16 entry points; in
+ * addition every operand (the fp32 sources, both planes, the outputs, dw, ws) must be 16-byte aligned, else
+ * VITAE_ERR_UNSUPPORTED_SHAPE.  Refused before the first launch, nothing written.  Per element |err| <= 2^-14 sum |a||b|.
+ * In a table of vitae_conv3d_pack_weights_multi the last word of an entry is its form: bit 0 transposed, VITAE_CONV3D_PACK_FORM_X3
+ * the two-plane destination (vitae_conv3d_packed_elems_x3 elements), written bit for bit as vitae_conv3d_pack_weight_x3 writes
+ * it; forms 0 and 1 are unchanged, every other value than 0, 1, 4, 5 is VITAE_ERR_INVALID_ARG. */
+#define VITAE_CONV3D_PACK_FORM_X3 4
+long vitae_conv3d_packed_elems_x3(int Cout, int Cin, int kd, int kh, int kw, int transposed);
+int vitae_conv3d_pack_weight_x3(const float* w, void* w16x2, int Cout, int Cin, int kd, int kh, int kw, int transposed, void* stream);
+/* [N, C, D, H, W] fp32 -> [N, D, H, W, C] fp32 (the network input of the fp32x3 route), bit for bit */
+int vitae_to_channels_last_f32(const float* x, float* out, int N, int C, int D, int H, int W, void* stream);
+int vitae_conv3d_fwd_x3(const float* x, const void* w16x2, float* y, void* y_bf16, int N, int D, int H, int W, int Cin, int Cout,
+                        int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream);
+int vitae_conv3d_bwd_input_x3(const float* dy, const void* w16x2t, float* dx, void* dx_bf16, int accumulate, int N, int D, int H, int W,
+                              int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream);
+int vitae_conv3d_bwd_weight_x3(const float* dy, const float* x, float* dw, float* ws, long ws_floats, int accumulate, int N, int D, int H,
+                               int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream);
 /* MaxPool3d(kernel 3, stride 2, padding 1), channels-last: x fp32 [N, D, H, W, C] -> y / y_bf16 [N, Do, Ho, Wo, C] (at least one) and
  * idx: one uint8 per output, the tap (kd_i * 3 + kh_i) * 3 + kw_i of the maximum.  Padding is -inf; the scan is torch's (d, h, w
  * ascending; a value replaces the maximum when it is greater or NaN).  bwd: each input voxel visits the <= 8 windows that contain

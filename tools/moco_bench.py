@@ -28,6 +28,10 @@ against on (14 B; 8 + 22 B for the weights that have a slot: the GEMM weights of
 the same loop.  Two tables, each of two models alternating in this process: kernels against the torch statements (as above), and the
 convolution operand store (``resnet.ConvPackStore``, one ``vitae_conv3d_pack_weights_multi`` launch per encoder and step) against a pack
 per convolution call (``VITAE_CONV_PACK_STORE=0``).
+
+    python tools/moco_bench.py arch=resnet precision=bf16,fp32x3 [batch=4,16] [reps=5] [inner=1]
+
+``precision=``: one ``MoCo_ResNet`` per listed precision of the encoders instead, the same step, alternating windows after 2 warm-ups.
 """
 import os
 import statistics
@@ -106,10 +110,11 @@ def windows(fns, reps, inner):
     return [(statistics.median(ts), min(ts), max(ts)) for ts in tss]
 
 
-def make(route, depth, kernels):
+def make(route, depth, kernels, precision='bf16'):
     if route == 'resnet':
         from vit_ae_plus_plus_amd.other_baselines.mocov3.moco.resent3d_base import generate_model
-        model = MoCo_ResNet(partial(generate_model, model_depth=10, n_input_channels=4), 256, 4096, 0.2).cuda().train()
+        kw = {} if precision == 'bf16' else dict(precision=precision)
+        model = MoCo_ResNet(partial(generate_model, model_depth=10, n_input_channels=4, **kw), 256, 4096, 0.2).cuda().train()
     else:
         enc = partial(VisionTransformer3D, in_chans=4, volume_size=96, depth=depth, **ROUTES[route])
         model = MoCo_ViT(enc, 256, 4096, 0.2).cuda().train()
@@ -139,7 +144,28 @@ def under(switch, fn, name='VITAE_WEIGHT_SHADOW'):
     return f
 
 
+def resnet_precision_main(batches, precisions, reps, inner):
+    """the routes of the 3-D ResNet under the same MoCo step, one model each, alternating"""
+    fmt = lambda t: f'{t[0]:.3f} ({t[1]:.3f} .. {t[2]:.3f})'
+    print('| MoCo_ResNet, ResNet-10 | batch / view | ' + ' | '.join(f'{p} ms (min .. max)' for p in precisions) + ' | last / first |')
+    print('|---|---|' + '---|' * (len(precisions) + 1))
+    for B in batches:
+        g = torch.Generator().manual_seed(B)
+        x1 = torch.randn(B, 4, 96, 96, 96, generator=g).cuda()
+        x2 = torch.randn(B, 4, 96, 96, 96, generator=g).cuda()
+        fns = [step_fn(*make('resnet', 0, True, p), x1, x2) for p in precisions]
+        for _ in range(2):
+            for f in fns:
+                f()
+        ts = windows(fns, reps, inner)
+        print(f'| step | {B} | ' + ' | '.join(fmt(t) for t in ts) + f' | {ts[-1][0] / ts[0][0]:.3f} |', flush=True)
+        del fns
+        torch.cuda.empty_cache()
+
+
 def resnet_main(batches, reps, inner):
+    if _option('precision', ''):
+        return resnet_precision_main(batches, _option('precision', '').split(','), reps, inner)
     fmt = lambda t: f'{t[0]:.3f} ({t[1]:.3f} .. {t[2]:.3f})'
     rows = []
     print('| MoCo_ResNet, ResNet-10 | batch / view | kernels ms (min .. max) | torch statements ms (min .. max) | ratio |')

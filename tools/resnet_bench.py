@@ -10,6 +10,10 @@ route; then a per-kernel table of one HIP step (every launch sequence of vit_ae_
 ``pack``: the HIP step with the per-model operand store (``resnet.ConvPackStore``: every stale convolution operand in one
 ``vitae_conv3d_pack_weights_multi`` launch per step) against a pack per convolution call (``VITAE_CONV_PACK_STORE=0``), two models
 alternating in this process.
+
+    python tools/resnet_bench.py precision [--batch B] [--iters N]
+
+``precision``: the HIP model on its two routes (``precision='bf16'`` and ``'fp32x3'``), one model each, alternating in this process.
 """
 import collections
 import os
@@ -164,6 +168,36 @@ def pack_rows(B):
           f'{seq.pack_store_of(models[1]).launches} pack launches in {ITERS + WARMUP} steps', flush=True)
 
 
+def precision_rows(B):
+    """The two routes of the HIP model, one model each, alternating: forward + backward and the step with Adam; kept MiB of each."""
+    x = torch.randn(B, CHANNELS, VOLUME, VOLUME, VOLUME, device='cuda')
+    y = torch.randint(0, 2, (B,), device='cuda')
+    crit = nn.CrossEntropyLoss(weight=torch.tensor([3.0, 1.0], device='cuda'))
+    models = [generate_model(10, n_classes=2, n_input_channels=CHANNELS, precision=p).cuda().train() for p in seq.PRECISIONS]
+    opts = [torch.optim.Adam(m.parameters(), lr=1e-4) for m in models]
+
+    def fb(i):
+        def f():
+            opts[i].zero_grad(set_to_none=True)
+            crit(models[i](x), y).backward()
+        return f
+
+    def step(i):
+        def f():
+            fb(i)()
+            opts[i].step()
+        return f
+
+    n = range(len(models))
+    tf, ts = timed_ab(*(fb(i) for i in n)), timed_ab(*(step(i) for i in n))
+    for i, p in enumerate(seq.PRECISIONS):
+        _, kept = seq.HipResNetRunner(models[i]).forward_keep(x)
+        print(f'resnet10 B={B} precision {p:7s}: forward+backward {tf[i][0]:.2f} ms ({tf[i][1]:.2f} .. {tf[i][2]:.2f}), step with Adam {ts[i][0]:.2f} ms '
+              f'({ts[i][1]:.2f} .. {ts[i][2]:.2f}), keeps {kept_mib(kept):.0f} MiB', flush=True)
+        del kept
+    print(f'resnet10 B={B}: {seq.PRECISIONS[1]} / {seq.PRECISIONS[0]} = {tf[1][0] / tf[0][0]:.2f} (forward+backward), {ts[1][0] / ts[0][0]:.2f} (step)', flush=True)
+
+
 def kernel_rows(B):
     """One HIP step with every launch sequence of vit_ae_plus_plus_amd.resnet timed on its own (synchronised before and after)."""
     table = collections.OrderedDict()
@@ -185,7 +219,7 @@ def kernel_rows(B):
     conv_label = lambda kind: lambda t, N, vol, conv, **k: (f'{kind} {conv.in_channels}->{conv.out_channels} k{conv.kernel_size[1]} '
                                                              f's{conv.stride[1]} in {vol}')
     saved = {n: wrap(n, l) for n, l in (('conv_fwd', conv_label('conv fwd')), ('conv_bwd_input', conv_label('conv dX')),
-                                        ('conv_bwd_weight', lambda d, x, N, vol, conv: conv_label('conv dW')(d, N, vol, conv)),
+                                        ('conv_bwd_weight', lambda d, x, N, vol, conv, **k: conv_label('conv dW')(d, N, vol, conv)),
                                         ('bn_tail_train', lambda x, res, bn, relu, w16: f'bn tail fwd {tuple(x.shape)}'),
                                         ('bn_tail_bwd', lambda dy, x, *a, **k: f'bn tail bwd {tuple(x.shape)}'))}
     try:
@@ -214,4 +248,6 @@ for B in ([BATCH] if BATCH else [4, 16]):
         kernel_rows(B)
     if 'pack' in ROWS:
         pack_rows(B)
+    if 'precision' in ROWS:
+        precision_rows(B)
     torch.cuda.empty_cache()

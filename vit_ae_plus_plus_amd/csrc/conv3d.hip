@@ -13,58 +13,9 @@
 //
 // Safety: a gather is issued only under its predicate (row in range, k < K, source voxel inside the volume), so no address outside
 // an operand is formed; offsets are 64-bit.  No LDS beyond a 343-entry tap table / a 64-row coordinate table.
-#include "common.hpp"
-#include "vitae_hip.h"
-
-#include <limits.h>
-#include <initializer_list>
+#include "conv3d.hpp"
 
 namespace {
-
-constexpr int KSTEP = VITAE_CONV3D_K_STEP;
-constexpr int MAX_TAPS = 7 * 7 * 7;
-constexpr int WCHUNK = VITAE_CONV3D_WGRAD_CHUNK;
-// Two-level accumulation: the MFMA chain runs FLUSH k-steps (128 k-values) in fp32 and is then added to a double total.  One fp32
-// chain over the stem's 1372 steps (all products of one sign) was 18 ulp off in the worst element, 4.6 x torch's blocked fp32 sum.
-constexpr int FLUSH = 8;
-
-__device__ __forceinline__ void flush_acc(f32x16& acc, double (&tot)[16]) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { tot[i] += (double)acc[i]; acc[i] = 0.f; }
-}
-
-struct ConvGeo {
-    int N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw;
-    int Do, Ho, Wo, taps;
-    long M, V;          // output rows N Do Ho Wo, input voxels N D H W
-    long K;             // taps * Cin
-};
-
-// VITAE_OK or the refusal; fills g
-int conv_geo(ConvGeo& g, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw) {
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return VITAE_ERR_INVALID_ARG;
-    if (kd < 1 || kh < 1 || kw < 1 || kd > 7 || kh > 7 || kw > 7) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    if (sd < 1 || sh < 1 || sw < 1 || sd > 2 || sh > 2 || sw > 2) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    if (pd < 0 || ph < 0 || pw < 0 || pd >= kd || ph >= kh || pw >= kw) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    if (Cout & 3) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    if (D + 2 * pd < kd || H + 2 * ph < kh || W + 2 * pw < kw) return VITAE_ERR_UNSUPPORTED_SHAPE;      // an output extent <= 0
-    g = ConvGeo{N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw};
-    g.Do = (D + 2 * pd - kd) / sd + 1; g.Ho = (H + 2 * ph - kh) / sh + 1; g.Wo = (W + 2 * pw - kw) / sw + 1;
-    g.taps = kd * kh * kw;
-    g.M = (long)N * g.Do * g.Ho * g.Wo;
-    g.V = (long)N * D * H * W;
-    g.K = (long)g.taps * Cin;
-    const long lim = (long)INT_MAX - 256;
-    if (g.M > lim || g.V > lim || g.K > lim || (long)g.taps * Cout > lim) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    return VITAE_OK;
-}
-
-inline long kpad(long K) { return (K + KSTEP - 1) / KSTEP * KSTEP; }
-inline int shift_of(int c) { return (c & (c - 1)) == 0 ? __builtin_ctz(c) : -1; }
-inline bool aligned16(std::initializer_list<const void*> ptrs) {
-    for (const void* q : ptrs) if ((uintptr_t)q & 15) return false;
-    return true;
-}
 
 // ------------------------------------------------------------------ packing
 __global__ __launch_bounds__(256) void conv3d_pack_kernel(const float* __restrict__ w, __bf16* __restrict__ out, int Cout, int Cin, int taps,
@@ -85,16 +36,20 @@ __global__ __launch_bounds__(256) void conv3d_pack_kernel(const float* __restric
 // Every operand of a network in one launch: the destinations laid end to end and cut into chunks of PACK_CHUNK elements; chunks[2 c],
 // chunks[2 c + 1] = the entry in which chunk c begins and the offset there in groups of 8.  A thread converts 8 consecutive k of one
 // row (a packed size is a multiple of 16, so a group lies in one row of one entry) with conv3d_pack_kernel's expression per element
-// and stores them as 16 bytes; it walks on to the next entry when its group lies behind the current one.
+// and stores them as 16 bytes; it walks on to the next entry when its group lies behind the current one.  The last word of an entry
+// is its form: bit 0 transposed, VITAE_CONV3D_PACK_FORM_X3 two planes per row [hi | lo] (2 Kp elements: the first Kp groups / 8 of a
+// row are bf16(w), the others bf16(w - float(bf16(w)))).
 static_assert(VITAE_CONV3D_PACK_CHUNK % (8 * 256) == 0, "a chunk is a whole number of groups per thread");
-struct PackEntry { const float* w; __bf16* out; long long Cout, Cin, kd, kh, kw, transposed; };
+struct PackEntry { const float* w; __bf16* out; long long Cout, Cin, kd, kh, kw, form; };
+constexpr long long FORM_X3 = VITAE_CONV3D_PACK_FORM_X3;
 constexpr int PACK_GROUPS = VITAE_CONV3D_PACK_CHUNK / 8;
 
 __host__ __device__ inline long pack_entry_groups(const PackEntry& e, int& taps, int& Kp) {
     taps = (int)(e.kd * e.kh * e.kw);
-    const long K = (long)taps * (e.transposed ? e.Cout : e.Cin);
+    const bool tr = e.form & 1;
+    const long K = (long)taps * (tr ? e.Cout : e.Cin);
     Kp = (int)((K + KSTEP - 1) / KSTEP * KSTEP);
-    return (e.transposed ? e.Cin : e.Cout) * (long)Kp / 8;
+    return (tr ? e.Cin : e.Cout) * (long)Kp / 8 * (e.form & FORM_X3 ? 2 : 1);
 }
 
 __global__ __launch_bounds__(256) void conv3d_pack_multi_kernel(const PackEntry* __restrict__ table, int n_entries, const int* __restrict__ chunks,
@@ -119,9 +74,13 @@ __global__ __launch_bounds__(256) void conv3d_pack_multi_kernel(const PackEntry*
             groups = pack_entry_groups(e, taps, Kp);
         }
         const long o = (i - start) * 8;
-        const int row = (int)(o / Kp), k0 = (int)(o % Kp);
+        const bool tr = e.form & 1, x3 = e.form & FORM_X3;
+        const long rowlen = x3 ? 2L * Kp : Kp;
+        const int row = (int)(o / rowlen), kk = (int)(o % rowlen);
+        const bool lo = kk >= Kp;                         // the second plane of a two-plane row
+        const int k0 = lo ? kk - Kp : kk;
         const int Cout = (int)e.Cout, Cin = (int)e.Cin;
-        const int inner = e.transposed ? Cout : Cin;      // k = tap * inner + c
+        const int inner = tr ? Cout : Cin;                // k = tap * inner + c
         bf16x8 h;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -129,10 +88,10 @@ __global__ __launch_bounds__(256) void conv3d_pack_multi_kernel(const PackEntry*
             float v = 0.f;
             if (k < taps * inner) {
                 const int tap = k / inner, c = k % inner;
-                const int co = e.transposed ? c : row, ci = e.transposed ? row : c;
+                const int co = tr ? c : row, ci = tr ? row : c;
                 v = e.w[((long)co * Cin + ci) * taps + tap];
             }
-            h[j] = (__bf16)v;
+            h[j] = lo ? (__bf16)(v - (float)(__bf16)v) : (__bf16)v;
         }
         *reinterpret_cast<bf16x8*>(e.out + o) = h;
     }
@@ -156,16 +115,6 @@ struct GatherArgs {
     int K, Kp, cs_shift;        // K = taps * Cs; Kp = K padded to the k step; log2(Cs) or -1
     int accum;                  // != 0: the result is added to what `out` holds
 };
-
-// One axis of the coordinate rule.  Forward: source = row * stride - pad + tap.  Input gradient: t = voxel + pad - tap must be a
-// non-negative multiple of the stride (1 or 2) and t / stride an existing output position.
-template <bool BWD>
-__device__ __forceinline__ bool conv_axis(int base, int tap, int stride, int extent, int& c) {
-    if (!BWD) { c = base + tap; return c >= 0 && c < extent; }
-    const int t = base - tap;
-    c = t >> (stride - 1);
-    return t >= 0 && (t & (stride - 1)) == 0 && c < extent;
-}
 
 template <int G, bool BWD>
 __global__ __launch_bounds__(256) void conv3d_gather_kernel(const GatherArgs a) {
@@ -314,21 +263,6 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_part_kernel(const __bf16* __
     }
 }
 
-// the partials in chunk order -> torch's [Cout, Cin, taps]
-__global__ __launch_bounds__(256) void conv3d_wgrad_sum_kernel(const float* __restrict__ ws, float* __restrict__ dw, int chunks, int Cout, int Cin,
-                                                               int taps, int accumulate) {
-    const long total = (long)Cout * Cin * taps;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;              // over [co][k = tap Cin + ci]: coalesced partial reads
-    if (i >= total) return;
-    double sd = 0.;
-    for (int z = 0; z < chunks; ++z) sd += (double)ws[(long)z * total + i];
-    const float s = (float)sd;
-    const int K = taps * Cin;
-    const int co = (int)(i / K), k = (int)(i % K), tap = k / Cin, ci = k % Cin;
-    const long o = ((long)co * Cin + ci) * taps + tap;
-    dw[o] = accumulate ? dw[o] + s : s;
-}
-
 // ------------------------------------------------------------------ MaxPool3d(3, 2, 1)
 __global__ __launch_bounds__(256) void maxpool3d_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, __bf16* __restrict__ y16,
                                                             unsigned char* __restrict__ idx, int D, int H, int W, int C, int Do, int Ho, int Wo,
@@ -456,18 +390,22 @@ extern "C" int vitae_conv3d_pack_weight(const float* w, void* w16, int Cout, int
 }
 
 namespace {
+inline long pack_form_elems(int Cout, int Cin, int kd, int kh, int kw, long long form) {
+    return vitae_conv3d_packed_elems(Cout, Cin, kd, kh, kw, (int)(form & 1)) * (form & FORM_X3 ? 2 : 1);
+}
+
 // VITAE_OK or the refusal of a pack table (host copy); total_groups: all destinations in groups of 8 elements
 int pack_multi_check(const long long* table, long n_entries, long& total_groups) {
     if (!table || n_entries <= 0 || n_entries > INT_MAX) return VITAE_ERR_INVALID_ARG;
     total_groups = 0;
     for (long t = 0; t < n_entries; ++t) {
         const long long* w = table + t * VITAE_CONV3D_PACK_ENTRY_WORDS;
-        const long long Cout = w[2], Cin = w[3], kd = w[4], kh = w[5], kw = w[6], tr = w[7];
-        if (!w[0] || !w[1] || Cout <= 0 || Cin <= 0 || Cout > INT_MAX || Cin > INT_MAX || (tr != 0 && tr != 1)) return VITAE_ERR_INVALID_ARG;
+        const long long Cout = w[2], Cin = w[3], kd = w[4], kh = w[5], kw = w[6], form = w[7], tr = form & 1;
+        if (!w[0] || !w[1] || Cout <= 0 || Cin <= 0 || Cout > INT_MAX || Cin > INT_MAX || (form & ~(1 | FORM_X3))) return VITAE_ERR_INVALID_ARG;
         if (kd < 1 || kh < 1 || kw < 1 || kd > 7 || kh > 7 || kw > 7 || (Cout & 3)) return VITAE_ERR_UNSUPPORTED_SHAPE;
         if (w[1] & 15) return VITAE_ERR_UNSUPPORTED_SHAPE;
         if (kpad(kd * kh * kw * (tr ? Cout : Cin)) > (long)INT_MAX - 256) return VITAE_ERR_UNSUPPORTED_SHAPE;
-        const long elems = vitae_conv3d_packed_elems((int)Cout, (int)Cin, (int)kd, (int)kh, (int)kw, (int)tr);
+        const long elems = pack_form_elems((int)Cout, (int)Cin, (int)kd, (int)kh, (int)kw, form);
         if (elems <= 0 || elems > VITAE_CONV3D_PACK_MAX_ELEMS) return VITAE_ERR_UNSUPPORTED_SHAPE;
         total_groups += elems / 8;
         if (total_groups * 8 > VITAE_CONV3D_PACK_MAX_ELEMS) return VITAE_ERR_UNSUPPORTED_SHAPE;
@@ -479,7 +417,7 @@ int pack_multi_check(const long long* table, long n_entries, long& total_groups)
 bool pack_multi_walk(const long long* table, long n_entries, long n_chunks, int* out, const int* check) {
     const auto groups_of = [&](long t) {
         const long long* w = table + t * VITAE_CONV3D_PACK_ENTRY_WORDS;
-        return vitae_conv3d_packed_elems((int)w[2], (int)w[3], (int)w[4], (int)w[5], (int)w[6], (int)w[7]) / 8;
+        return pack_form_elems((int)w[2], (int)w[3], (int)w[4], (int)w[5], (int)w[6], w[7]) / 8;
     };
     long t = 0, off = 0, groups = groups_of(0);           // where the next chunk begins: entry, group offset inside it
     for (long c = 0; c < n_chunks; ++c) {

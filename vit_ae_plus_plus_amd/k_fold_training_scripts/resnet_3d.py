@@ -10,7 +10,9 @@ The sub-modules only HOLD parameters and buffers: the arithmetic runs in ``ResNe
 ``eval()`` mode or under ``no_grad``; ``forward_features`` is the same below ``fc``, and with ``batch_stats=True`` under ``no_grad`` the
 training arithmetic with nothing kept: a MoCo momentum encoder).  Calling a sub-module on its own raises ``VitaeError`` — there is no
 torch fallback.  Operands of the convolutions and of the head are bf16 with fp32 accumulation: the counterpart of the reference
-script's autocast region.
+script's autocast region.  ``precision='fp32x3'`` (keyword-only; ``set_precision`` later) is the parity-grade route: every fp32 operand
+of the convolutions and of the head enters the bf16 MFMA as hi + lo halves (three products), ~1e-5 from a float64 run instead of
+percent.  An exact-fp32 convolution is not built: any other value raises ``VitaeError``.
 
 Served: depths 10 / 18 / 34 (BasicBlock), shortcut 'B', any ``widen_factor`` whose widths stay multiples of 4.
 Refused at construction (``NotImplementedError``): depths 50 - 200 (Bottleneck) and shortcut 'A'.
@@ -20,7 +22,7 @@ import torch.nn as nn
 
 from .._abi import CONSTS, VitaeError
 from ..model.vit import _HeadFunction, hip_linear
-from ..resnet import HipResNetRunner
+from ..resnet import HipResNetRunner, check_precision
 
 
 def get_inplanes():
@@ -99,8 +101,9 @@ class _BodyFunction(torch.autograd.Function):
 class ResNet(nn.Module):
 
     def __init__(self, block, layers, block_inplanes, n_input_channels=3, conv1_t_size=7, conv1_t_stride=1, no_max_pool=False,
-                 shortcut_type='B', widen_factor=1.0, n_classes=400):
+                 shortcut_type='B', widen_factor=1.0, n_classes=400, *, precision='bf16'):
         super().__init__()
+        self.precision = check_precision(precision)
         if block is not BasicBlock:
             raise NotImplementedError('only BasicBlock networks (depths 10 / 18 / 34) are built for MI355X')
         if shortcut_type != 'B':
@@ -160,8 +163,14 @@ class ResNet(nn.Module):
         with torch.no_grad():
             return runner.infer(x)
 
+    def set_precision(self, precision):
+        """``'bf16'`` | ``'fp32x3'`` from the next forward on (anything else: ``VitaeError``).  The packed operands of the other route
+        are dropped when the new one first asks for its own."""
+        self.precision = check_precision(precision)
+        return self
+
     def forward(self, x):
-        prec = CONSTS['VITAE_PREC_BF16']
+        prec = CONSTS['VITAE_PREC_BF16X3' if check_precision(self.precision) == 'fp32x3' else 'VITAE_PREC_BF16']
         feat = self.forward_features(x)
         if self.training and torch.is_grad_enabled():
             return _HeadFunction.apply(feat, self.fc.weight, self.fc.bias, prec)

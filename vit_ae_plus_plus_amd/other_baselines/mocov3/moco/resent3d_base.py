@@ -10,10 +10,10 @@ from ....k_fold_training_scripts.resnet_3d import BasicBlock, Bottleneck, conv1x
 class ResNet(_base.ResNet):
 
     def __init__(self, block, layers, block_inplanes, n_input_channels=3, conv1_t_size=7, conv1_t_stride=1, no_max_pool=False,
-                 shortcut_type='B', widen_factor=1.0, num_classes=400):
+                 shortcut_type='B', widen_factor=1.0, num_classes=400, *, precision='bf16'):
         super().__init__(block, layers, block_inplanes, n_input_channels=n_input_channels, conv1_t_size=conv1_t_size,
                          conv1_t_stride=conv1_t_stride, no_max_pool=no_max_pool, shortcut_type=shortcut_type, widen_factor=widen_factor,
-                         n_classes=num_classes)
+                         n_classes=num_classes, precision=precision)
 
 
 def generate_model(model_depth, **kwargs):
