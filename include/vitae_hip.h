@@ -737,7 +737,7 @@ long vitae_conv3d_wgrad_ws_floats(int N, int D, int H, int W, int Cin, int Cout,
                                   int pd, int ph, int pw);
 int vitae_conv3d_bwd_weight(const void* dy16, const void* x16, float* dw, float* ws, long ws_floats, int accumulate, int N, int D, int H,
                             int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream);
-/* ---- fp32x3 route of the 3-D ResNet (csrc/conv3d_x3.hip; additive to ABI 57: no existing entry point changes) ----------------
+/* ---- fp32x3 route of the 3-D ResNet (csrc/conv3d.hip, operand policy OpX3; additive to ABI 57: no existing entry point changes) ---
  * The same gather-GEMMs with fp32 sources and split operands.  Every fp32 value v enters the bf16 MFMA as hi = bf16(v) and
  * lo = bf16(v - float(hi)); per k-step three v_mfma_f32_32x32x16_bf16 go into the one accumulator in this fixed order:
  * a_lo b_hi, a_hi b_lo, a_hi b_hi (the cross terms first; lo.lo is dropped).  The row operand (x, dy) is the route's fp32

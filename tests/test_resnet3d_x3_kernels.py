@@ -1,4 +1,4 @@
-"""The split-operand convolutions of the fp32x3 route (csrc/conv3d_x3.hip) through the C ABI, where they can go wrong.
+"""The split-operand convolutions of the fp32x3 route (csrc/conv3d.hip's OpX3 instances) through the C ABI, where they can go wrong.
 
 Every fp32 operand enters the bf16 MFMA as hi = bf16(v), lo = bf16(v - hi); a product is hi.hi + hi.lo + lo.hi.
 

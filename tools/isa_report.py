@@ -1,12 +1,14 @@
 """Per-kernel code-generation comparison of two builds: did a source change move any instruction?
 
     hipcc <build.py's FLAGS> --cuda-device-only -S csrc/X.hip -o before/X.s        (one .s per translation unit, both trees)
-    python tools/isa_report.py before/ after/ [--only SUBSTRING]
+    python tools/isa_report.py before/ after/ [--only SUBSTRING] [--rename BEFORE=AFTER ...]
 
 Takes two device assemblies, or two directories of them (a kernel is found in whichever file of a side holds it, so a side may be
-one translation unit and the other several).  For every kernel symbol: instruction count, whether the instruction text is identical,
-if not the difference of the opcode multisets (after minus before), and the kernel metadata that decides occupancy.  The tool only
-compares the two sides; it knows no instruction by name.  Exit status 1 when the symbol sets or any metadata differ."""
+one translation unit and the other several).  Kernels are paired by symbol; one that the change renamed (a new template parameter,
+say) is paired by hand with --rename, BEFORE and AFTER each a substring that picks one demangled name of its side.  For every
+kernel symbol: instruction count, whether the instruction text is identical, if not the difference of the opcode multisets (after
+minus before), and the kernel metadata that decides occupancy.  The tool only compares the two sides; it knows no instruction by
+name.  Exit status 1 when the symbol sets or any metadata differ."""
 from __future__ import annotations
 
 import argparse
@@ -85,9 +87,19 @@ def main() -> int:
     ap.add_argument('before')
     ap.add_argument('after')
     ap.add_argument('--only', default='', help='report kernels whose demangled name contains this')
+    ap.add_argument('--rename', action='append', default=[], metavar='BEFORE=AFTER',
+                    help='pair the one kernel of the "before" side whose demangled name contains BEFORE with the one of the "after" side '
+                         'whose demangled name contains AFTER (a kernel the change renamed); repeatable')
     a = ap.parse_args()
     A, B = side(a.before), side(a.after)
     names = demangle(sorted(set(A) | set(B)))
+    for r in a.rename:
+        old, _, new = r.partition('=')
+        ka, kb = [k for k in A if old in names[k]], [k for k in B if new in names[k]]
+        if not old or not new or len(ka) != 1 or len(kb) != 1 or ka[0] in B or kb[0] in A:
+            ap.error(f'--rename {r}: {len(ka)} kernels before, {len(kb)} after (one of each wanted, neither of them present on the other side)')
+        A[kb[0]] = A.pop(ka[0])
+        names[kb[0]] = f'{names.pop(ka[0])}  ->  {names[kb[0]]}'
     bad = same = 0
     shown = [k for k in sorted(names, key=names.get) if a.only in names[k]]
     for k in shown:

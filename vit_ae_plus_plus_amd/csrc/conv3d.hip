@@ -11,31 +11,195 @@
 // MFMA operand maps (32x32x16 bf16): lane l, r = l & 31, h = l >> 5 holds A[row r][k = 8 h + j] and B[k = 8 h + j][col r], j = 0..7;
 // the result has col = l & 31 and row = (reg & 3) + 8 (reg >> 2) + 4 h.
 //
+// Two routes share every kernel body here through an operand policy (OpBf16, OpX3 below).  bf16: sources and packed weight are bf16,
+// one MFMA per k-step.  fp32x3: every fp32 value v enters the bf16 MFMA as two halves, hi = bf16(v) and lo = bf16(v - float(hi)), so
+// v is carried to ~2^-16 relative instead of 2^-8.  A product is formed as three terms into ONE accumulator, in this fixed order per
+// k-step:
+//
+//     acc = mfma(a_lo, b_hi, acc);   acc = mfma(a_hi, b_lo, acc);   acc = mfma(a_hi, b_hi, acc);      (cross terms first, then hi.hi)
+//
+// lo.lo (<= 2^-16 of the product) is dropped.  a = the gathered row operand: the route's fp32 channels-last activation or gradient,
+// split in registers by the lane that gathered it — no producer writes extra planes (32 bytes as two 16-byte loads of consecutive
+// addresses when Cin % 8 == 0, 16 bytes when Cin % 4 == 0, else element by element).  b = the weight, packed once per optimiser step
+// as two bf16 planes per row, [hi (Kp) | lo (Kp)], in the same k = tap * inner + c order with zero tails.  The weight gradient splits
+// both of its fp32 operands (dy, x) in registers.  A non-finite fp32 source gives a NaN lo half (inf - inf), so it poisons what reads it.
+//
 // Safety: a gather is issued only under its predicate (row in range, k < K, source voxel inside the volume), so no address outside
 // an operand is formed; offsets are 64-bit.  No LDS beyond a 343-entry tap table / a 64-row coordinate table.
-#include "conv3d.hpp"
+#include "common.hpp"
+#include "vitae_hip.h"
+
+#include <limits.h>
+#include <initializer_list>
 
 namespace {
 
+constexpr int KSTEP = VITAE_CONV3D_K_STEP;
+constexpr int MAX_TAPS = 7 * 7 * 7;
+constexpr int WCHUNK = VITAE_CONV3D_WGRAD_CHUNK;
+// Two-level accumulation: the MFMA chain runs FLUSH k-steps (128 k-values; three MFMAs each on the fp32x3 route) in fp32 and is then
+// added to a double total.  One fp32 chain over the stem's 1372 steps (all products of one sign) was 18 ulp off in the worst element,
+// 4.6 x torch's blocked fp32 sum.
+constexpr int FLUSH = 8;
+
+__device__ __forceinline__ void flush_acc(f32x16& acc, double (&tot)[16]) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { tot[i] += (double)acc[i]; acc[i] = 0.f; }
+}
+
+struct ConvGeo {
+    int N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw;
+    int Do, Ho, Wo, taps;
+    long M, V;          // output rows N Do Ho Wo, input voxels N D H W
+    long K;             // taps * Cin
+};
+
+// VITAE_OK or the refusal; fills g
+inline int conv_geo(ConvGeo& g, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw) {
+    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return VITAE_ERR_INVALID_ARG;
+    if (kd < 1 || kh < 1 || kw < 1 || kd > 7 || kh > 7 || kw > 7) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (sd < 1 || sh < 1 || sw < 1 || sd > 2 || sh > 2 || sw > 2) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (pd < 0 || ph < 0 || pw < 0 || pd >= kd || ph >= kh || pw >= kw) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (Cout & 3) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    if (D + 2 * pd < kd || H + 2 * ph < kh || W + 2 * pw < kw) return VITAE_ERR_UNSUPPORTED_SHAPE;      // an output extent <= 0
+    g = ConvGeo{N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw};
+    g.Do = (D + 2 * pd - kd) / sd + 1; g.Ho = (H + 2 * ph - kh) / sh + 1; g.Wo = (W + 2 * pw - kw) / sw + 1;
+    g.taps = kd * kh * kw;
+    g.M = (long)N * g.Do * g.Ho * g.Wo;
+    g.V = (long)N * D * H * W;
+    g.K = (long)g.taps * Cin;
+    const long lim = (long)INT_MAX - 256;
+    if (g.M > lim || g.V > lim || g.K > lim || (long)g.taps * Cout > lim) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    return VITAE_OK;
+}
+
+inline long kpad(long K) { return (K + KSTEP - 1) / KSTEP * KSTEP; }
+inline int shift_of(int c) { return (c & (c - 1)) == 0 ? __builtin_ctz(c) : -1; }
+inline bool aligned16(std::initializer_list<const void*> ptrs) {
+    for (const void* q : ptrs) if ((uintptr_t)q & 15) return false;
+    return true;
+}
+
+// One axis of the coordinate rule.  Forward: source = row * stride - pad + tap.  Input gradient: t = voxel + pad - tap must be a
+// non-negative multiple of the stride (1 or 2) and t / stride an existing output position.
+template <bool BWD>
+__device__ __forceinline__ bool conv_axis(int base, int tap, int stride, int extent, int& c) {
+    if (!BWD) { c = base + tap; return c >= 0 && c < extent; }
+    const int t = base - tap;
+    c = t >> (stride - 1);
+    return t >= 0 && (t & (stride - 1)) == 0 && c < extent;
+}
+
+// ------------------------------------------------------------------ operand policies: all that differs between the two routes
+// Src: the element of the gathered operands.  PLANES: bf16 planes of Kp per packed weight row.  AFrag / BFrag: the 8 k-values of a
+// lane as gathered (indexable by element) / as the packed weight is loaded; both are zero when value-initialised.  gather<G>: the
+// g-th group of G consecutive values at p.  mma(a, b, acc): a gathered; b the weight or, in the weight gradient, gathered as well.
+struct OpBf16 {
+    using Src = __bf16;
+    static constexpr int PLANES = 1;
+    using AFrag = bf16x8;
+    using BFrag = bf16x8;
+    static __device__ __forceinline__ BFrag load_b(const __bf16* wrow, int k0, int) { return *reinterpret_cast<const bf16x8*>(wrow + k0); }
+    template <int G>
+    static __device__ __forceinline__ void gather(AFrag& a, const Src* p, int g) {
+        if (G == 8) a = *reinterpret_cast<const bf16x8*>(p);
+        else if (G == 4) {
+            const bf16x4 q = *reinterpret_cast<const bf16x4*>(p);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) a[4 * g + e] = q[e];
+        } else a[g] = *p;
+    }
+    static __device__ __forceinline__ f32x16 mma(const AFrag& a, const BFrag& b, f32x16 acc) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+    }
+};
+
+struct OpX3 {
+    using Src = float;
+    static constexpr int PLANES = 2;
+    struct AFrag {
+        float v[8];
+        __device__ __forceinline__ float& operator[](int j) { return v[j]; }
+    };
+    struct BFrag { bf16x8 hi, lo; };
+    static __device__ __forceinline__ BFrag load_b(const __bf16* wrow, int k0, int Kp) {
+        return {*reinterpret_cast<const bf16x8*>(wrow + k0), *reinterpret_cast<const bf16x8*>(wrow + Kp + k0)};
+    }
+    template <int G>
+    static __device__ __forceinline__ void gather(AFrag& a, const Src* p, int g) {
+        if (G == 8) {
+            const f32x4 q0 = *reinterpret_cast<const f32x4*>(p), q1 = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { a.v[e] = q0[e]; a.v[4 + e] = q1[e]; }
+        } else if (G == 4) {
+            const f32x4 q = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) a.v[4 * g + e] = q[e];
+        } else a.v[g] = *p;
+    }
+    static __device__ __forceinline__ BFrag split(const AFrag& a) {
+        BFrag s;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            s.hi[j] = (__bf16)a.v[j];
+            s.lo[j] = (__bf16)(a.v[j] - (float)s.hi[j]);
+        }
+        return s;
+    }
+    static __device__ __forceinline__ f32x16 mma(const BFrag& a, const BFrag& b, f32x16 acc) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.lo, b.hi, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.lo, acc, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.hi, acc, 0, 0, 0);
+    }
+    static __device__ __forceinline__ f32x16 mma(const AFrag& a, const BFrag& b, f32x16 acc) { return mma(split(a), b, acc); }
+    static __device__ __forceinline__ f32x16 mma(const AFrag& a, const AFrag& b, f32x16 acc) { return mma(split(a), split(b), acc); }
+};
+
 // ------------------------------------------------------------------ packing
+// the fp32 value at (row, k) of a packed weight: k = tap * inner + c, zero behind K; w is torch's [Cout, Cin, taps]
+__device__ __forceinline__ float packed_value(const float* __restrict__ w, int Cout, int Cin, int taps, bool transposed, int row, int k) {
+    const int inner = transposed ? Cout : Cin;
+    if (k >= taps * inner) return 0.f;
+    const int tap = k / inner, c = k % inner;
+    const int co = transposed ? c : row, ci = transposed ? row : c;
+    return w[((long)co * Cin + ci) * taps + tap];
+}
+
+// [rows][Kp] (PLANES = 1) or [rows][hi (Kp) | lo (Kp)] (PLANES = 2)
+template <int PLANES>
 __global__ __launch_bounds__(256) void conv3d_pack_kernel(const float* __restrict__ w, __bf16* __restrict__ out, int Cout, int Cin, int taps,
                                                           int Kp, int transposed, long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;              // over [row][k] of ONE plane
     if (i >= total) return;
     const int row = (int)(i / Kp), k = (int)(i % Kp);
-    const int inner = transposed ? Cout : Cin;          // k = tap * inner + c
-    float v = 0.f;
-    if (k < taps * inner) {
-        const int tap = k / inner, c = k % inner;
-        const int co = transposed ? c : row, ci = transposed ? row : c;
-        v = w[((long)co * Cin + ci) * taps + tap];
+    const float v = packed_value(w, Cout, Cin, taps, transposed, row, k);
+    const __bf16 hi = (__bf16)v;
+    if (PLANES == 1) out[i] = hi;
+    else {
+        out[2L * row * Kp + k] = hi;
+        out[2L * row * Kp + Kp + k] = (__bf16)(v - (float)hi);
     }
-    out[i] = (__bf16)v;
+}
+
+// VITAE_OK and the padded row length of one weight, or the refusal
+int pack_geo(const float* w, const void* out, int Cout, int Cin, int kd, int kh, int kw, int transposed, long& Kp) {
+    if (!w || !out || Cout <= 0 || Cin <= 0) return VITAE_ERR_INVALID_ARG;
+    if (kd < 1 || kh < 1 || kw < 1 || kd > 7 || kh > 7 || kw > 7 || (Cout & 3)) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    Kp = kpad((long)kd * kh * kw * (transposed ? Cout : Cin));
+    return Kp > (long)INT_MAX - 256 ? VITAE_ERR_UNSUPPORTED_SHAPE : VITAE_OK;
+}
+
+template <int PLANES>
+int run_pack(const float* w, void* out, int Cout, int Cin, int taps, long Kp, int transposed, void* stream) {
+    const long total = (long)(transposed ? Cin : Cout) * Kp;
+    hipLaunchKernelGGL(conv3d_pack_kernel<PLANES>, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, reinterpret_cast<__bf16*>(out), Cout,
+                       Cin, taps, (int)Kp, transposed ? 1 : 0, total);
+    return vitae_launch_status();
 }
 
 // Every operand of a network in one launch: the destinations laid end to end and cut into chunks of PACK_CHUNK elements; chunks[2 c],
 // chunks[2 c + 1] = the entry in which chunk c begins and the offset there in groups of 8.  A thread converts 8 consecutive k of one
-// row (a packed size is a multiple of 16, so a group lies in one row of one entry) with conv3d_pack_kernel's expression per element
+// row (a packed size is a multiple of 16, so a group lies in one row of one entry), each through packed_value as conv3d_pack_kernel,
 // and stores them as 16 bytes; it walks on to the next entry when its group lies behind the current one.  The last word of an entry
 // is its form: bit 0 transposed, VITAE_CONV3D_PACK_FORM_X3 two planes per row [hi | lo] (2 Kp elements: the first Kp groups / 8 of a
 // row are bf16(w), the others bf16(w - float(bf16(w)))).
@@ -79,45 +243,48 @@ __global__ __launch_bounds__(256) void conv3d_pack_multi_kernel(const PackEntry*
         const int row = (int)(o / rowlen), kk = (int)(o % rowlen);
         const bool lo = kk >= Kp;                         // the second plane of a two-plane row
         const int k0 = lo ? kk - Kp : kk;
-        const int Cout = (int)e.Cout, Cin = (int)e.Cin;
-        const int inner = tr ? Cout : Cin;                // k = tap * inner + c
         bf16x8 h;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int k = k0 + j;
-            float v = 0.f;
-            if (k < taps * inner) {
-                const int tap = k / inner, c = k % inner;
-                const int co = tr ? c : row, ci = tr ? row : c;
-                v = e.w[((long)co * Cin + ci) * taps + tap];
-            }
+            const float v = packed_value(e.w, (int)e.Cout, (int)e.Cin, taps, tr, row, k0 + j);
             h[j] = lo ? (__bf16)(v - (float)(__bf16)v) : (__bf16)v;
         }
         *reinterpret_cast<bf16x8*>(e.out + o) = h;
     }
 }
 
-__global__ __launch_bounds__(256) void channels_last_bf16_kernel(const float* __restrict__ x, __bf16* __restrict__ out, int C, long S, long total) {
+template <class T>
+__global__ __launch_bounds__(256) void channels_last_kernel(const float* __restrict__ x, T* __restrict__ out, int C, long S, long total) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;      // output index: (n S + s) C + c
     if (i >= total) return;
     const int c = (int)(i % C);
     const long ns = i / C, n = ns / S, s = ns % S;
-    out[i] = (__bf16)x[(n * C + c) * S + s];
+    out[i] = (T)x[(n * C + c) * S + s];
+}
+
+template <class T>
+int run_channels_last(const float* x, T* out, int N, int C, int D, int H, int W, void* stream) {
+    if (!x || !out || N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return VITAE_ERR_INVALID_ARG;
+    const long S = (long)D * H * W, total = (long)N * S * C;
+    if (total > (long)INT_MAX * 128) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    hipLaunchKernelGGL(channels_last_kernel<T>, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, out, C, S, total);
+    return vitae_launch_status();
 }
 
 // ------------------------------------------------------------------ forward / input gradient: one gather-GEMM
+template <class Op>
 struct GatherArgs {
-    const __bf16* src; const __bf16* wpk; float* out; __bf16* out16;
+    const typename Op::Src* src; const __bf16* wpk; float* out; __bf16* out16;
     int Ds, Hs, Ws, Cs;         // source volume of one sample, its channels
     int Dr, Hr, Wr;             // row space of one sample
     int M, Nout;                // rows, output columns
     int kd, kh, kw, sd, sh, sw, pd, ph, pw;
-    int K, Kp, cs_shift;        // K = taps * Cs; Kp = K padded to the k step; log2(Cs) or -1
+    int K, Kp, cs_shift;        // K = taps * Cs; Kp = K padded to the k step (one plane of a packed row); log2(Cs) or -1
     int accum;                  // != 0: the result is added to what `out` holds
 };
 
-template <int G, bool BWD>
-__global__ __launch_bounds__(256) void conv3d_gather_kernel(const GatherArgs a) {
+template <class Op, int G, bool BWD>
+__global__ __launch_bounds__(256) void conv3d_gather_kernel(const GatherArgs<Op> a) {
     __shared__ int tab[MAX_TAPS];                                    // tap -> kd_i << 16 | kh_i << 8 | kw_i
     const int taps = a.kd * a.kh * a.kw;
     for (int t = threadIdx.x; t < taps; t += 256) {
@@ -141,7 +308,7 @@ __global__ __launch_bounds__(256) void conv3d_gather_kernel(const GatherArgs a) 
     }
     const int co = blockIdx.y * 32 + l31;                            // the column of this lane's B fragment
     const bool cok = co < a.Nout;
-    const __bf16* wrow = a.wpk + (long)(cok ? co : 0) * a.Kp + 8 * hi;
+    const __bf16* wrow = a.wpk + (long)(cok ? co : 0) * ((long)Op::PLANES * a.Kp) + 8 * hi;
     const long nbase = (long)n * a.Ds;
 
     f32x16 acc;
@@ -150,10 +317,9 @@ __global__ __launch_bounds__(256) void conv3d_gather_kernel(const GatherArgs a) 
     for (int i = 0; i < 16; ++i) { acc[i] = 0.f; tot[i] = 0.; }
     int chain = 0;
     for (int k0 = 0; k0 < a.Kp; k0 += KSTEP) {
-        bf16x8 av, bv;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { av[j] = (__bf16)0.f; bv[j] = (__bf16)0.f; }
-        if (cok) bv = *reinterpret_cast<const bf16x8*>(wrow + k0);
+        typename Op::AFrag av{};
+        typename Op::BFrag bv{};
+        if (cok) bv = Op::load_b(wrow, k0, a.Kp);
 #pragma unroll
         for (int g = 0; g < 8 / G; ++g) {
             const int k = k0 + 8 * hi + g * G;
@@ -165,15 +331,9 @@ __global__ __launch_bounds__(256) void conv3d_gather_kernel(const GatherArgs a) 
             const bool ok = conv_axis<BWD>(bd, t >> 16, a.sd, a.Ds, d) & conv_axis<BWD>(bh, (t >> 8) & 255, a.sh, a.Hs, h) &
                             conv_axis<BWD>(bw, t & 255, a.sw, a.Ws, w);
             if (!ok) continue;
-            const __bf16* p = a.src + (((nbase + d) * a.Hs + h) * a.Ws + w) * a.Cs + ci;
-            if (G == 8) av = *reinterpret_cast<const bf16x8*>(p);
-            else if (G == 4) {
-                const bf16x4 q = *reinterpret_cast<const bf16x4*>(p);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) av[4 * g + e] = q[e];
-            } else av[g] = *p;
+            Op::template gather<G>(av, a.src + (((nbase + d) * a.Hs + h) * a.Ws + w) * a.Cs + ci, g);
         }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
+        acc = Op::mma(av, bv, acc);
         if (++chain == FLUSH) { flush_acc(acc, tot); chain = 0; }
     }
     flush_acc(acc, tot);
@@ -190,19 +350,32 @@ __global__ __launch_bounds__(256) void conv3d_gather_kernel(const GatherArgs a) 
     }
 }
 
-template <bool BWD>
-void launch_gather(const GatherArgs& a, hipStream_t st) {
+// forward (src = x, out = y) or input gradient (src = dy, wpk = the transposed form, out = dx) of a checked geometry; the launch status
+template <class Op, bool BWD>
+int run_gather(const ConvGeo& g, const void* src, const void* wpk, float* out, void* out16, int accumulate, void* stream) {
+    GatherArgs<Op> a;
+    a.src = reinterpret_cast<const typename Op::Src*>(src); a.wpk = reinterpret_cast<const __bf16*>(wpk);
+    a.out = out; a.out16 = reinterpret_cast<__bf16*>(out16);
+    if (!BWD) { a.Ds = g.D; a.Hs = g.H; a.Ws = g.W; a.Cs = g.Cin; a.Dr = g.Do; a.Hr = g.Ho; a.Wr = g.Wo; a.M = (int)g.M; a.Nout = g.Cout; }
+    else { a.Ds = g.Do; a.Hs = g.Ho; a.Ws = g.Wo; a.Cs = g.Cout; a.Dr = g.D; a.Hr = g.H; a.Wr = g.W; a.M = (int)g.V; a.Nout = g.Cin; }
+    a.kd = g.kd; a.kh = g.kh; a.kw = g.kw; a.sd = g.sd; a.sh = g.sh; a.sw = g.sw; a.pd = g.pd; a.ph = g.ph; a.pw = g.pw;
+    a.K = g.taps * a.Cs; a.Kp = (int)kpad(a.K); a.cs_shift = shift_of(a.Cs); a.accum = accumulate ? 1 : 0;
     const dim3 grid(cdiv(a.M, 128), cdiv(a.Nout, 32));
-    if (a.Cs % 8 == 0) hipLaunchKernelGGL((conv3d_gather_kernel<8, BWD>), grid, dim3(256), 0, st, a);
-    else if (a.Cs % 4 == 0) hipLaunchKernelGGL((conv3d_gather_kernel<4, BWD>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv3d_gather_kernel<1, BWD>), grid, dim3(256), 0, st, a);
+    const hipStream_t st = (hipStream_t)stream;
+    if (a.Cs % 8 == 0) hipLaunchKernelGGL((conv3d_gather_kernel<Op, 8, BWD>), grid, dim3(256), 0, st, a);
+    else if (a.Cs % 4 == 0) hipLaunchKernelGGL((conv3d_gather_kernel<Op, 4, BWD>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv3d_gather_kernel<Op, 1, BWD>), grid, dim3(256), 0, st, a);
+    return vitae_launch_status();
 }
 
 // ------------------------------------------------------------------ weight gradient
 // Workgroup = (128 k-columns: 32 per wave) x (32 output channels) x (one chunk of rows).  MFMA: A[row = co][k = m] = dy16[m, co],
 // B[k = m][col = kcol] = x16[src(m, tap(kcol)), ci(kcol)].  The 8 rows of a lane's fragments are the same for the 32 lanes of a
-// half wave; their decoded coordinates come from a 64-row table in LDS that the first wave refills every 64 rows.
-__global__ __launch_bounds__(256) void conv3d_wgrad_part_kernel(const __bf16* __restrict__ dy16, const __bf16* __restrict__ x16,
+// half wave; their decoded coordinates come from a 64-row table in LDS that the first wave refills every 64 rows.  Both operands are
+// gathered, element by element (Op::Src; on the fp32x3 route both are split in registers, by Op::mma after the element loop: a split
+// inside the loop costs one route or the other registers or instructions, whichever way it is written — LABNOTES.md).
+template <class Op>
+__global__ __launch_bounds__(256) void conv3d_wgrad_part_kernel(const typename Op::Src* __restrict__ dy16, const typename Op::Src* __restrict__ x16,
                                                                 float* __restrict__ ws, const ConvGeo g) {
     __shared__ int4 rowtab[64];                                       // n (or -1 past the chunk), od sd - pd, oh sh - ph, ow sw - pw
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
@@ -238,19 +411,19 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_part_kernel(const __bf16* __
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             if (mb + ks * KSTEP >= m_end) break;                      // uniform over the workgroup
-            bf16x8 av, bv;
+            typename Op::AFrag av, bv;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int ml = ks * KSTEP + 8 * hi + j;
                 const int4 e = rowtab[ml];
                 const bool rok = e.x >= 0;
-                av[j] = (__bf16)0.f; bv[j] = (__bf16)0.f;
-                if (rok && cok) av[j] = dy16[(long)(mb + ml) * g.Cout + co];
                 const int d = e.y + tkd, h = e.z + tkh, w = e.w + tkw;
+                av[j] = 0.f; bv[j] = 0.f;
+                if (rok && cok) av[j] = dy16[(long)(mb + ml) * g.Cout + co];
                 if (rok && kok && d >= 0 && d < g.D && h >= 0 && h < g.H && w >= 0 && w < g.W)
                     bv[j] = x16[((((long)e.x * g.D + d) * g.H + h) * g.W + w) * g.Cin + ci];
             }
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
+            acc = Op::mma(av, bv, acc);
         }
     }
     flush_acc(acc, tot);
@@ -261,6 +434,39 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_part_kernel(const __bf16* __
         const int c = crow0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
         if (c < g.Cout) ws[((long)blockIdx.z * g.Cout + c) * K + kcol] = (float)tot[r];
     }
+}
+
+// the weight gradient's partials in chunk order -> torch's [Cout, Cin, taps]
+__global__ __launch_bounds__(256) void conv3d_wgrad_sum_kernel(const float* __restrict__ ws, float* __restrict__ dw, int chunks, int Cout, int Cin,
+                                                               int taps, int accumulate) {
+    const long total = (long)Cout * Cin * taps;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;              // over [co][k = tap Cin + ci]: coalesced partial reads
+    if (i >= total) return;
+    double sd = 0.;
+    for (int z = 0; z < chunks; ++z) sd += (double)ws[(long)z * total + i];
+    const float s = (float)sd;
+    const int K = taps * Cin;
+    const int co = (int)(i / K), k = (int)(i % K), tap = k / Cin, ci = k % Cin;
+    const long o = ((long)co * Cin + ci) * taps + tap;
+    dw[o] = accumulate ? dw[o] + s : s;
+}
+
+// VITAE_OK and the chunk count of a checked geometry, or the refusal of the caller's workspace
+int wgrad_chunks(const ConvGeo& g, long ws_floats, int& chunks) {
+    chunks = cdiv(g.M, WCHUNK);
+    if (ws_floats < (long)chunks * g.Cout * g.K) return VITAE_ERR_INVALID_ARG;
+    if (chunks > 65535) return VITAE_ERR_UNSUPPORTED_SHAPE;                     // grid.z
+    return VITAE_OK;
+}
+
+template <class Op>
+int run_wgrad(const ConvGeo& g, int chunks, const void* dy, const void* x, float* dw, float* ws, int accumulate, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(conv3d_wgrad_part_kernel<Op>, dim3(cdiv(g.K, 128), cdiv(g.Cout, 32), chunks), dim3(256), 0, st,
+                       reinterpret_cast<const typename Op::Src*>(dy), reinterpret_cast<const typename Op::Src*>(x), ws, g);
+    const long total = (long)g.Cout * g.K;
+    hipLaunchKernelGGL(conv3d_wgrad_sum_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, ws, dw, chunks, g.Cout, g.Cin, g.taps, accumulate ? 1 : 0);
+    return vitae_launch_status();
 }
 
 // ------------------------------------------------------------------ MaxPool3d(3, 2, 1)
@@ -350,17 +556,6 @@ __global__ __launch_bounds__(256) void rows_mean_bwd_kernel(const float* __restr
     if (dx16) dx16[i] = (__bf16)v;
 }
 
-GatherArgs gather_args(const ConvGeo& g, bool bwd, const void* src, const void* wpk, float* out, void* out16) {
-    GatherArgs a;
-    a.src = reinterpret_cast<const __bf16*>(src); a.wpk = reinterpret_cast<const __bf16*>(wpk);
-    a.out = out; a.out16 = reinterpret_cast<__bf16*>(out16);
-    if (!bwd) { a.Ds = g.D; a.Hs = g.H; a.Ws = g.W; a.Cs = g.Cin; a.Dr = g.Do; a.Hr = g.Ho; a.Wr = g.Wo; a.M = (int)g.M; a.Nout = g.Cout; }
-    else { a.Ds = g.Do; a.Hs = g.Ho; a.Ws = g.Wo; a.Cs = g.Cout; a.Dr = g.D; a.Hr = g.H; a.Wr = g.W; a.M = (int)g.V; a.Nout = g.Cin; }
-    a.kd = g.kd; a.kh = g.kh; a.kw = g.kw; a.sd = g.sd; a.sh = g.sh; a.sw = g.sw; a.pd = g.pd; a.ph = g.ph; a.pw = g.pw;
-    a.K = g.taps * a.Cs; a.Kp = (int)kpad(a.K); a.cs_shift = shift_of(a.Cs); a.accum = 0;
-    return a;
-}
-
 int pool_geo(int N, int D, int H, int W, int C, int& Do, int& Ho, int& Wo, long& in_total, long& out_total) {
     if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0) return VITAE_ERR_INVALID_ARG;
     Do = (D - 1) / 2 + 1; Ho = (H - 1) / 2 + 1; Wo = (W - 1) / 2 + 1;            // (X + 2 - 3) / 2 + 1
@@ -378,15 +573,20 @@ extern "C" long vitae_conv3d_packed_elems(int Cout, int Cin, int kd, int kh, int
 }
 
 extern "C" int vitae_conv3d_pack_weight(const float* w, void* w16, int Cout, int Cin, int kd, int kh, int kw, int transposed, void* stream) {
-    if (!w || !w16 || Cout <= 0 || Cin <= 0) return VITAE_ERR_INVALID_ARG;
-    if (kd < 1 || kh < 1 || kw < 1 || kd > 7 || kh > 7 || kw > 7 || (Cout & 3)) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    const int taps = kd * kh * kw;
-    const long Kp = kpad((long)taps * (transposed ? Cout : Cin));
-    if (Kp > (long)INT_MAX - 256) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    const long total = (long)(transposed ? Cin : Cout) * Kp;
-    hipLaunchKernelGGL(conv3d_pack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, reinterpret_cast<__bf16*>(w16), Cout, Cin,
-                       taps, (int)Kp, transposed ? 1 : 0, total);
-    return vitae_launch_status();
+    long Kp;
+    if (const int rc = pack_geo(w, w16, Cout, Cin, kd, kh, kw, transposed, Kp)) return rc;
+    return run_pack<1>(w, w16, Cout, Cin, kd * kh * kw, Kp, transposed, stream);
+}
+
+extern "C" long vitae_conv3d_packed_elems_x3(int Cout, int Cin, int kd, int kh, int kw, int transposed) {
+    return 2 * vitae_conv3d_packed_elems(Cout, Cin, kd, kh, kw, transposed);
+}
+
+extern "C" int vitae_conv3d_pack_weight_x3(const float* w, void* w16x2, int Cout, int Cin, int kd, int kh, int kw, int transposed, void* stream) {
+    long Kp;
+    if (const int rc = pack_geo(w, w16x2, Cout, Cin, kd, kh, kw, transposed, Kp)) return rc;
+    if ((uintptr_t)w16x2 & 15) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    return run_pack<2>(w, w16x2, Cout, Cin, kd * kh * kw, Kp, transposed, stream);
 }
 
 namespace {
@@ -463,12 +663,11 @@ extern "C" int vitae_conv3d_pack_weights_multi(const long long* table_host, cons
 }
 
 extern "C" int vitae_to_channels_last_bf16(const float* x, void* x16, int N, int C, int D, int H, int W, void* stream) {
-    if (!x || !x16 || N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0) return VITAE_ERR_INVALID_ARG;
-    const long S = (long)D * H * W, total = (long)N * S * C;
-    if (total > (long)INT_MAX * 128) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    hipLaunchKernelGGL(channels_last_bf16_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<__bf16*>(x16), C, S,
-                       total);
-    return vitae_launch_status();
+    return run_channels_last(x, reinterpret_cast<__bf16*>(x16), N, C, D, H, W, stream);
+}
+
+extern "C" int vitae_to_channels_last_f32(const float* x, float* out, int N, int C, int D, int H, int W, void* stream) {
+    return run_channels_last(x, out, N, C, D, H, W, stream);
 }
 
 extern "C" int vitae_conv3d_fwd(const void* x16, const void* w16, float* y, void* y_bf16, int N, int D, int H, int W, int Cin, int Cout, int kd,
@@ -477,8 +676,16 @@ extern "C" int vitae_conv3d_fwd(const void* x16, const void* w16, float* y, void
     ConvGeo g;
     if (const int rc = conv_geo(g, N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw)) return rc;
     if (!aligned16({x16, w16, y, y_bf16})) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    launch_gather<false>(gather_args(g, false, x16, w16, y, y_bf16), (hipStream_t)stream);
-    return vitae_launch_status();
+    return run_gather<OpBf16, false>(g, x16, w16, y, y_bf16, 0, stream);
+}
+
+extern "C" int vitae_conv3d_fwd_x3(const float* x, const void* w16x2, float* y, void* y_bf16, int N, int D, int H, int W, int Cin, int Cout, int kd,
+                                   int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream) {
+    if (!x || !w16x2 || (!y && !y_bf16)) return VITAE_ERR_INVALID_ARG;
+    ConvGeo g;
+    if (const int rc = conv_geo(g, N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw)) return rc;
+    if (!aligned16({x, w16x2, y, y_bf16})) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    return run_gather<OpX3, false>(g, x, w16x2, y, y_bf16, 0, stream);
 }
 
 extern "C" int vitae_conv3d_bwd_input(const void* dy16, const void* w16t, float* dx, void* dx_bf16, int accumulate, int N, int D, int H, int W,
@@ -487,10 +694,16 @@ extern "C" int vitae_conv3d_bwd_input(const void* dy16, const void* w16t, float*
     ConvGeo g;
     if (const int rc = conv_geo(g, N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw)) return rc;
     if (!aligned16({dy16, w16t, dx, dx_bf16})) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    GatherArgs a = gather_args(g, true, dy16, w16t, dx, dx_bf16);
-    a.accum = accumulate ? 1 : 0;
-    launch_gather<true>(a, (hipStream_t)stream);
-    return vitae_launch_status();
+    return run_gather<OpBf16, true>(g, dy16, w16t, dx, dx_bf16, accumulate, stream);
+}
+
+extern "C" int vitae_conv3d_bwd_input_x3(const float* dy, const void* w16x2t, float* dx, void* dx_bf16, int accumulate, int N, int D, int H, int W,
+                                         int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, void* stream) {
+    if (!dy || !w16x2t || (!dx && !dx_bf16) || (accumulate && !dx)) return VITAE_ERR_INVALID_ARG;
+    ConvGeo g;
+    if (const int rc = conv_geo(g, N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw)) return rc;
+    if (!aligned16({dy, w16x2t, dx, dx_bf16})) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    return run_gather<OpX3, true>(g, dy, w16x2t, dx, dx_bf16, accumulate, stream);
 }
 
 extern "C" long vitae_conv3d_wgrad_ws_floats(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd,
@@ -505,16 +718,22 @@ extern "C" int vitae_conv3d_bwd_weight(const void* dy16, const void* x16, float*
                                        void* stream) {
     if (!dy16 || !x16 || !dw || !ws) return VITAE_ERR_INVALID_ARG;
     ConvGeo g;
+    int chunks;
     if (const int rc = conv_geo(g, N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw)) return rc;
-    const int chunks = cdiv(g.M, WCHUNK);
-    if (ws_floats < (long)chunks * Cout * g.K) return VITAE_ERR_INVALID_ARG;
-    if (chunks > 65535) return VITAE_ERR_UNSUPPORTED_SHAPE;                     // grid.z
-    const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(conv3d_wgrad_part_kernel, dim3(cdiv(g.K, 128), cdiv(Cout, 32), chunks), dim3(256), 0, st,
-                       reinterpret_cast<const __bf16*>(dy16), reinterpret_cast<const __bf16*>(x16), ws, g);
-    const long total = (long)Cout * g.K;
-    hipLaunchKernelGGL(conv3d_wgrad_sum_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, ws, dw, chunks, Cout, Cin, g.taps, accumulate ? 1 : 0);
-    return vitae_launch_status();
+    if (const int rc = wgrad_chunks(g, ws_floats, chunks)) return rc;
+    return run_wgrad<OpBf16>(g, chunks, dy16, x16, dw, ws, accumulate, stream);
+}
+
+extern "C" int vitae_conv3d_bwd_weight_x3(const float* dy, const float* x, float* dw, float* ws, long ws_floats, int accumulate, int N, int D, int H,
+                                          int W, int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw,
+                                          void* stream) {
+    if (!dy || !x || !dw || !ws) return VITAE_ERR_INVALID_ARG;
+    ConvGeo g;
+    int chunks;
+    if (const int rc = conv_geo(g, N, D, H, W, Cin, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw)) return rc;
+    if (const int rc = wgrad_chunks(g, ws_floats, chunks)) return rc;
+    if (!aligned16({dy, x, dw, ws})) return VITAE_ERR_UNSUPPORTED_SHAPE;
+    return run_wgrad<OpX3>(g, chunks, dy, x, dw, ws, accumulate, stream);
 }
 
 extern "C" int vitae_maxpool3d_fwd(const float* x, float* y, void* y_bf16, void* idx, int N, int D, int H, int W, int C, void* stream) {

@@ -17,8 +17,8 @@ The bf16 operands of the convolutions live in a per-model ``ConvPackStore``: all
 ``vitae_conv3d_pack_weights_multi`` launch when the first of them is asked for.  ``forward_batch_stats`` is the training arithmetic with
 nothing kept (a MoCo momentum encoder).
 
-``precision='fp32x3'`` (``ResNet(..., precision=)`` / ``set_precision``) is the parity-grade route: the same sequence on the kernels of
-csrc/conv3d_x3.hip.  A convolution reads the fp32 tensor the sequence holds anyway (the BatchNorm tail's ``y``, the pooled stem, the
+``precision='fp32x3'`` (``ResNet(..., precision=)`` / ``set_precision``) is the parity-grade route: the same sequence on the split-operand
+instances of csrc/conv3d.hip's kernels.  A convolution reads the fp32 tensor the sequence holds anyway (the BatchNorm tail's ``y``, the pooled stem, the
 fp32 ``dx``) and splits it in registers; no bf16 activation copy is allocated or kept.  The weights are packed as two bf16 planes
 (form ``transposed | VITAE_CONV3D_PACK_FORM_X3`` of the store).
 """
