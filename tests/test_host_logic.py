@@ -236,3 +236,21 @@ def test_fit_split_shrinks_to_capacity_and_caches_per_key():
     site = lambda epi: 1 if (epi & 15) == EPI_GELU else split('c', 5)       # (_g16_fwd, _lin_fwd)
     assert [site(EPI_NONE), site(EPI_GELU | 16), site(EPI_NONE)] == [5, 1, 5] and cache['c'] == 5
     assert [1 if (e & 15) == EPI_GELU else split('d', 5) for e in (EPI_GELU, EPI_NONE)] == [1, 5]      # GELU first: nothing cached for it
+
+
+def test_environment_switches_are_the_documented_ones():
+    """Every VITAE_* name the Python package reads from the environment has a row in DESIGN.md's table of Python-side switches
+    (section 3d), and every row is still read: a new knob cannot arrive, and a retired one cannot linger, unseen."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    read = set()
+    for d, _, files in os.walk(os.path.join(root, 'vit_ae_plus_plus_amd')):
+        for f in files:
+            if f.endswith('.py'):
+                with open(os.path.join(d, f)) as fh:
+                    read |= set(re.findall(r'''environ(?:\.get\(|\[)\s*['"](VITAE_\w+)['"]''', fh.read()))
+    with open(os.path.join(root, 'DESIGN.md')) as fh:
+        section = re.search(r'^### 3d\. Python-side switches\n(.*?)^###? ', fh.read(), flags=re.S | re.M).group(1)
+    table = re.findall(r'^\| `(VITAE_\w+)` \|', section, flags=re.M)
+    assert len(table) == len(set(table)) and len(table) >= 12
+    assert set(table) == read, (sorted(read - set(table)), sorted(set(table) - read))

@@ -135,34 +135,19 @@ class HipMAEEngine:
         dims = (D, Dd, self.Hm, self.Hmd, cfg.patch_dim)
         self.act16 = (self.prec == PREC['bf16'] and all(v % 64 == 0 for v in dims)
                       and self.hd in (32, 64) and self.hdd in (32, 64))
-        self.wgrad_side = os.environ.get('VITAE_WGRAD_SIDE', '1') != '0'
-        self.target_fork = os.environ.get('VITAE_TARGET_FORK', 'start')
-        # What fc1 saves for the fc2 input gradient is bf16 (VITAE_EPI_AUX_BF16) in bf16 mode, at EVERY size (default on since the end of
-        # round 4: batch 4 4.50 -> 4.43 ms, batch 32 10.66 -> 10.58, patch 8 10.90 -> 10.84 once the big-tile epilogue took the aux type
-        # as a template parameter; VITAE_HPRE_BF16=0 keeps fp32).  Two documented bf16-mode deviations ride on it: the backward's GELU'
-        # comes from a bf16 value (since round 5: GELU'(fp32 pre-activation) rounded once, VITAE_EPI_AUX_DERIV), and decoder_pred's
-        # bias gradient is the column sum of the bf16 loss gradient.  The bf16 test bounds (tests/test_gpu_model.py) were recorded
-        # with both in place.
-        self._hpre16_env = os.environ.get('VITAE_HPRE_BF16', 'auto')
-        self.hpre16 = False
-        self._aux16 = 0
         # What fc1's epilogue saves for the backward (round 5): GELU'(pre-activation) instead of the pre-activation itself
         # (VITAE_EPI_AUX_DERIV) — the gate that gives GELU gives GELU' for one more FMA, and the fc2 input-gradient epilogue becomes
         # a multiply: its ~20 VALU operations per element were 11 of the 46 us of that launch at batch 32 (tools/epi_ablate.py).
         # fp32 aux: the same value bit for bit; bf16 aux: GELU' of the fp32 pre-activation, rounded once (was GELU' of the rounded one).
-        self._auxd = _C['VITAE_EPI_AUX_DERIV'] if os.environ.get('VITAE_AUX_DERIV', '1') != '0' else 0
-        self.fc1_bias_by_wgrad = os.environ.get('VITAE_FC1_BIAS_BY_WGRAD', '1') != '0'   # (see _block_bwd16)
+        self._auxd = _C['VITAE_EPI_AUX_DERIV']
+        # What fc1 saves for the fc2 input gradient is bf16 (VITAE_EPI_AUX_BF16) on the bf16-activation route, at EVERY size (since the
+        # end of round 4: batch 4 4.50 -> 4.43 ms, batch 32 10.66 -> 10.58, patch 8 10.90 -> 10.84 once the big-tile epilogue took the
+        # aux type as a template parameter).  Two documented bf16-mode deviations ride on it: the backward's GELU' comes from a bf16
+        # value (since round 5: GELU'(fp32 pre-activation) rounded once), and decoder_pred's bias gradient is the column sum of the
+        # bf16 loss gradient.  The bf16 test bounds (tests/test_gpu_model.py) were recorded with both in place.
+        self._aux16 = (_C['VITAE_EPI_AUX_BF16'] if self.act16 else 0) | self._auxd
         self._init_w2()
-        # the gradient norm's matrix share is accumulated by the weight-gradient epilogues themselves (vitae_gemm_glds_set_wgrad_sqnorm)
-        # instead of a pass over each bucket (45 us per bucket, the last one exposed behind the backward); single process only — a
-        # data-parallel norm is the norm of the REDUCED gradients
-        self.epi_norm = self.act16 and os.environ.get('VITAE_EPI_GRADNORM', '1') != '0'
-        # q | k | v leave the qkv GEMM in bf16 only and the attention kernels read that (no fp32 qkv in HBM: the GEMM epilogue is
-        # bound by its output bytes, and the kernels no longer convert while staging); needs the one-launch attention backward
-        self.qkv16 = self.act16 and os.environ.get('VITAE_QKV_BF16', '1') != '0'
-        self.qkv16_long = os.environ.get('VITAE_QKV_BF16_LONG', '1') != '0'     # (see _qkv16_ok)
         self.opt_state16 = os.environ.get('VITAE_OPT_STATE16', '1') != '0'      # (see _state16_ok)
-        self.sq_spread = os.environ.get('VITAE_SQ_SPREAD', '1') != '0'          # (see train_phase)
         self.buffers = buffers   # pos_embed, decoder_pos_embed, BN running stats (device tensors)
         f32 = dict(dtype=torch.float32, device=device)
         # ring of pinned staging buffers: the host may run a few steps ahead of the stream, so the
@@ -196,31 +181,29 @@ class HipMAEEngine:
         self._taps_c = self.taps.ctypes.data
         # fp32x3: the GEMMs of the fp32 schedule on the wave-specialised kernel whose producer waves split the fp32 operands
         # (vitae_gemm_wsx3: in-launch split-K — its workspaces start with zeroed tickets — and bias gradients beside the weight gradients)
-        self.x3ws = self.prec == PREC['fp32x3'] and os.environ.get('VITAE_X3_WS', '1') != '0'
+        self.x3ws = self.prec == PREC['fp32x3']
+        # the gradient norm's matrix share is accumulated by the weight-gradient epilogues themselves (vitae_gemm_glds_set_wgrad_sqnorm)
+        # instead of a pass over each bucket (45 us per bucket, the last one exposed behind the backward); single process only — a
+        # data-parallel norm is the norm of the REDUCED gradients.
         # fp32x3: the weight-gradient launches of vitae_gemm_wsx3 add their squares to the norm as well; WHICH matrices they serve depends
         # on the shapes (_x3_ok), so the covered ranges are recorded as the launches are enqueued (_x3_cov) and a bucket reads the rest
-        if self.x3ws and os.environ.get('VITAE_EPI_GRADNORM', '1') != '0':
-            self.epi_norm = True
+        self.epi_norm = self.act16 or self.x3ws
         self._x3_cov = []
         self.ws = torch.empty(1 << 24, **f32)   # split-K scratch (64 MiB)
         # (tickets + partial tiles of vitae_gemm_wsx3, one per stream; NOT shared with the older kernels, which park plain partials at offset 0)
         self.ws_x3 = {k: torch.zeros(n, **f32) for k, n in (('main', 1 << 23), ('pside', 1 << 22), ('wside', 1 << 22))} if self.x3ws else None
         self.ws16 = torch.zeros(1 << 24, **f32)  # LDS-DMA GEMMs: tile tickets (kept zero by the kernels) + partial tiles
-        self.attn_bias_colsum = os.environ.get('VITAE_ATTN_BIAS_COLSUM', '1') != '0'
         # predictor Linears on bf16 operands (LDS-DMA GEMMs) instead of the fp32-activation kernel (round 4: 6 launches of 70-110 us on
         # the predictor branch at batch 32, beside a chain that has no spare CUs there)
-        self.pred16 = self.act16 and (cfg.embed_dim % 64 == 0) and os.environ.get('VITAE_PREDICTOR_BF16', '1') != '0'
+        self.pred16 = self.act16
         self.ws16_side = torch.zeros(1 << 22, **f32) if self.pred16 else None
         # grouped weight gradients of a block (many token rows) on the wgrad side stream: they fill the CUs the dependent chain's
         # 168-220-tile launches leave idle; two alternating sets of dy operands, a set is rewritten two blocks later
-        self.wgrad_group_side = os.environ.get('VITAE_WGRAD_GROUP_SIDE', '1') == '1'
-        self.ws16_wside = torch.zeros(1 << 24, **f32) if (self.act16 and self.wgrad_group_side) else None
+        self.ws16_wside = torch.zeros(1 << 24, **f32) if self.act16 else None
+        # LayerNorm backward through partial records (no atomics), at EVERY size (round 6): the records of all LayerNorms of a step are
+        # summed by ONE launch in front of the optimiser's tail (``_ln_flush``), not by one per backward phase on the dependent chain
+        # (that form lost to the 3 D float atomics per workgroup at batch 4: 10.8 + 4 x 13 us against 10.2)
         self.ln_part_on = os.environ.get('VITAE_LN_PART', '1') != '0'
-        # LayerNorm backward through partial records (no atomics) from this many elements on.  Round 6: at EVERY size — the records of all
-        # LayerNorms of a step are summed by ONE launch in front of the optimiser's tail (``ln_flush_once``), not by one per backward
-        # phase on the dependent chain (that form lost to the 3 D float atomics per workgroup at batch 4: 10.8 + 4 x 13 us against 10.2)
-        self.ln_part_min = int(float(os.environ.get('VITAE_LN_PART_MIN', '0')))
-        self.ln_flush_once = os.environ.get('VITAE_LN_FLUSH_ONCE', '1') != '0'
         self._ln_pending = []
         self.B = None
         self.buf: Dict[str, torch.Tensor] = {}
@@ -247,7 +230,6 @@ class HipMAEEngine:
         self._opt_pending = False
         self._pred_pending = False
         self._pred_joined = False   # the predictor branch was joined by backward_dec(part='top')
-        self.overlap_wgrad = True
         self._wg_events: Dict[str, torch.cuda.Event] = {}
         self._wg_pending = set()
         self._wire_ready = False
@@ -441,8 +423,8 @@ class HipMAEEngine:
         self.hp[_C['VITAE_HP_STEP']] = float(step)
 
     # ------------------------------------------------------------------ workspace
-    _WS_ATTRS = ('B', 'keep', 'Be', 'Ne', 'Nd', 'Me', 'Md', 'Mpe', 'Mpd', 'Mpt', 'Mpl', 'R', 'mask_sum', 'edge_count', 'buf', 'hpre16', '_aux16')
-    _WS_MAX = int(os.environ.get('VITAE_WORKSPACES', '4'))
+    _WS_ATTRS = ('B', 'keep', 'Be', 'Ne', 'Nd', 'Me', 'Md', 'Mpe', 'Mpd', 'Mpt', 'Mpl', 'R', 'mask_sum', 'edge_count', 'buf')
+    _WS_MAX = 4
 
     def _alloc(self, B: int, mask_ratio: float):
         cfg = self.cfg
@@ -468,8 +450,6 @@ class HipMAEEngine:
         Ne, Nd, Be = keep + 1, L + 1, self.Be
         Me, Md = Be * Ne, B * Nd
         self.Ne, self.Nd, self.Me, self.Md = Ne, Nd, Me, Md
-        self.hpre16 = self.act16 and self._hpre16_env != '0'      # (end of round 4: a gain at every size — batch 32 10.66 -> 10.58 ms, patch 8 10.90 -> 10.84)
-        self._aux16 = (CONSTS['VITAE_EPI_AUX_BF16'] if self.hpre16 else 0) | self._auxd
         dev = self.device
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         b = self.buf = {}
@@ -483,21 +463,21 @@ class HipMAEEngine:
         b['tok'] = f(Be * keep, D)
         b['dtok'] = f(Be * keep, D)
 
-        def stack(pre, depth, M, d, h, N, hd):
-            q32 = not (self.act16 and self._qkv16_ok(N, hd))   # fp32 q | k | v and their gradient exist only when the bf16 copy is not the operand
+        def stack(pre, depth, M, d, h):
+            q32 = not self.act16   # fp32 q | k | v and their gradient exist only when the bf16 copy is not the operand
             b[pre + 'x'] = [f(M, d) for _ in range(depth + 1)]
             for i in range(depth):
                 q = f'{pre}{i}.'
                 b[q + 'y1'], b[q + 'mean1'], b[q + 'rstd1'] = f(M, d), f(M), f(M)
                 b[q + 'qkv'], b[q + 'o'] = (f(M, 3 * d) if q32 else None), f(M, d)
                 b[q + 'xmid'], b[q + 'y2'], b[q + 'mean2'], b[q + 'rstd2'] = f(M, d), f(M, d), f(M), f(M)
-                b[q + 'hpre'] = torch.empty(M, h, dtype=torch.bfloat16, device=dev) if self.hpre16 else f(M, h)
+                b[q + 'hpre'] = torch.empty(M, h, dtype=torch.bfloat16, device=dev) if self.act16 else f(M, h)
                 b[q + 'act'] = f(M, h)
             b[pre + 'dx'], b[pre + 'dy'], b[pre + 'do'] = f(M, d), f(M, d), f(M, d)
             b[pre + 'dh'], b[pre + 'dqkv'] = f(M, h), (f(M, 3 * d) if q32 else None)
 
-        stack('enc', cfg.depth, Me, D, self.Hm, self.Ne, self.hd)
-        stack('dec', cfg.decoder_depth, Md, Dd, self.Hmd, self.Nd, self.hdd)
+        stack('enc', cfg.depth, Me, D, self.Hm)
+        stack('dec', cfg.decoder_depth, Md, Dd, self.Hmd)
         if self.act16:
             # bf16 GEMM operands, token rows padded to 64 with zeros (wgrad reduces over the padded count)
             z16 = lambda *s: torch.zeros(*s, dtype=torch.bfloat16, device=dev)
@@ -506,14 +486,14 @@ class HipMAEEngine:
                 for i in range(depth):
                     q = f'{pre}{i}.'
                     b[q + 'y1_16'], b[q + 'o_16'], b[q + 'y2_16'], b[q + 'act_16'] = z16(Mp, d), z16(Mp, d), z16(Mp, d), z16(Mp, h)
-                    if self.qkv16:
-                        b[q + 'qkv_16'] = z16(Mp, 3 * d)
+                    # q | k | v leave the qkv GEMM in bf16 only and the attention kernels read that (no fp32 qkv in HBM: the GEMM
+                    # epilogue is bound by its output bytes, and the kernels no longer convert while staging)
+                    b[q + 'qkv_16'] = z16(Mp, 3 * d)
                 b[pre + 'dx_16'], b[pre + 'dh_16'], b[pre + 'dqkv_16'] = z16(Mp, d), z16(Mp, h), z16(Mp, 3 * d)
                 if self._grouped(Mp, d):
                     b[pre + 'dx_16b'] = z16(Mp, d)
-                    if self.wgrad_group_side:
-                        for nm, w in (('dx_16', d), ('dx_16b', d), ('dh_16', h), ('dqkv_16', 3 * d)):
-                            b[pre + nm + '_alt'] = z16(Mp, w)
+                    for nm, w in (('dx_16', d), ('dx_16b', d), ('dh_16', h), ('dqkv_16', 3 * d)):
+                        b[pre + nm + '_alt'] = z16(Mp, w)
             b['dn_16'] = z16(self.Mpd, Dd)
             b['dpred_16'] = z16(self.Mpd, P)
             b['patches_16'], b['dtok_16'] = z16(self.Mpt, P), z16(self.Mpt, D)
@@ -525,7 +505,7 @@ class HipMAEEngine:
             if cfg.contrastive and self.pred16:
                 # predictor on the LDS-DMA GEMMs: bf16 copies of its activations / their gradients (2 R = Me rows, zero pad rows)
                 b['pr_16'], b['dp_16'], b['dph_16'] = z16(self.Mpe, D), z16(self.Mpe, D), z16(self.Mpe, D)
-        if self.ln_part_on and max(Me * D, Md * Dd) >= self.ln_part_min:
+        if self.ln_part_on:
             # LayerNorm backward: one record of column partials [d gamma | d beta | colsum(dx)] per workgroup and LayerNorm instance
             for pre_, depth, M_, d_ in (('blocks.', cfg.depth, Me, D), ('decoder_blocks.', cfg.decoder_depth, Md, Dd)):
                 G = lib.vitae_layernorm_bwd_part_records(M_)
@@ -670,12 +650,12 @@ class HipMAEEngine:
                     lib.vitae_colsum_accum(_ptr(dy), N, _ptr(db), M, N, self.stream)
 
     def _lin_bwd_w(self, dy, x, dw, db, M, N, K, tag=None):
-        """dW (+)= dy^T x.  With ``tag`` (and overlap enabled) the GEMM is enqueued on the wgrad side stream:
+        """dW (+)= dy^T x.  With ``tag`` (and no ``gemm_timer``) the GEMM is enqueued on the wgrad side stream:
         it only needs dy / x, which are final when this is called, and nobody reads dW before the end of the
         backward phase.  ``tag`` names the dy buffer so that ``_wg_fence(tag)`` can be placed in front of the
         kernel that next overwrites it."""
         s = self._split(N, K, M)
-        side = tag is not None and self.overlap_wgrad and self.gemm_timer is None
+        side = tag is not None and self.gemm_timer is None
         ws = self.ws
         if side and s > 1:      # a split reduction beside the chain needs scratch of its own (the chain's GEMMs use self.ws)
             ws, s_main, key = self.ws_wside, s, ('wside', N, K, M)
@@ -724,14 +704,14 @@ class HipMAEEngine:
             return
         # the bias gradient colsum(dy) goes with the weight gradient (both only read dy; on the wgrad side stream when that overlaps):
         # as a separate launch on the main chain it was 84 x 11 us = 0.9 ms of the fp32-mode step
-        w_db = db if ((tag is not None and self.overlap_wgrad) or self.x3ws) else None
+        w_db = db if (tag is not None or self.x3ws) else None
         self._lin_bwd_w(dy, x, dw, w_db, M, N, K, tag=tag)
         self._lin_bwd_x(dy, w, dx, M, N, K, epi=epi, aux=aux, accumulate=dx_accumulate, db=None if w_db is not None else db)
 
     def _colsum_beside(self, x, ld, out, M, N, tag):
         """out[n] += colsum(x) on the wgrad side stream: a bias gradient that nothing on the main chain waits for until
         the end of the phase (``_wg_join``); ``tag`` names the buffer it reads, for ``_wg_fence``."""
-        if not self.overlap_wgrad or self.gemm_timer is not None:
+        if self.gemm_timer is not None:
             lib.vitae_colsum_accum(_ptr(x), ld, _ptr(out), M, N, self.stream)
             return
         self.wside.wait_stream(torch.cuda.current_stream(self.device))
@@ -764,11 +744,9 @@ class HipMAEEngine:
 
     def _ln_bwd(self, dy, x, pre, mean, rstd, dx, M, D, dx_accumulate, dx16=None, dx_colsum=None):
         """LayerNorm backward.  Default (round 4): no atomics — the launch leaves its d(gamma) / d(beta) / colsum(dx) partials as
-        records in ``ln_part`` and ``_ln_flush`` (once per backward phase) adds the records of every LayerNorm of the phase into the
+        records in ``ln_part`` and ``_ln_flush`` (once per step) adds the records of every LayerNorm of the step into the
         gradient arena with one launch; nothing reads those gradients before the optimiser's tail."""
-        # (few rows: the atomic kernel — its 3 D atomics per workgroup are cheaper than the reduce launches: batch 4 measured 10.8 us +
-        # 4 x 13 us of reduces per step against 10.2 us)
-        if self.ln_part_on and D in (256, 512, 768, 1024) and self.buf and M * D >= self.ln_part_min:
+        if self.ln_part_on and D in (256, 512, 768, 1024) and self.buf:
             G = lib.vitae_layernorm_bwd_part_records(M)
             part = self.buf.get('lnpart.' + pre)
             if part is None or part.numel() < G * 3 * D:      # (a LayerNorm the workspace does not know: allocated on first use)
@@ -782,12 +760,12 @@ class HipMAEEngine:
                                 _ptr(self.g[pre + 'weight']), _ptr(self.g[pre + 'bias']), _ptr(dx16), _ptr(dx_colsum),
                                 M, D, dx_accumulate, self.stream)
 
-    def _ln_flush(self, final=False):
+    def _ln_flush(self):
         """Add the pending LayerNorm partial records into the gradient arena: once per step, at the end of the last backward phase
-        (``final``; nothing reads these vector gradients earlier — the optimiser's tail and the data-parallel exchange of the
-        token / vector bucket both follow it), or at the end of every phase (``ln_flush_once`` off)."""
+        (``backward_tail``; nothing reads these vector gradients earlier — the optimiser's tail and the data-parallel exchange of
+        the token / vector bucket both follow it)."""
         pend = self._ln_pending
-        if not pend or (self.ln_flush_once and not final):
+        if not pend:
             return
         u64 = lambda k: np.array([t[k] for t in pend], dtype=np.uint64)
         i32 = lambda k: np.array([t[k] for t in pend], dtype=np.int32)
@@ -899,38 +877,31 @@ class HipMAEEngine:
                                            epi, _ptr(aux), _ptr(dx_colsum), _ptr(dy_colsum), int(dx_accumulate), int(self._accum), s,
                                            self.ws16.data_ptr(), self.ws16.numel(), self.stream)
 
-    def _wgrad_group(self, items, M, Mpad, bias=None):
+    def _wgrad_group(self, items, M, Mpad):
         """The weight gradients of one block's Linears in ONE launch (csrc/gemm_bt.hip: gemm_bt_wgrad_group_kernel).
-        ``items``: [(dy16, x16, dw, N, K)]; ``bias``: {index: bias-gradient tensor} for column sums of dy taken beside it."""
+        ``items``: [(dy16, x16, dw, N, K)]; no bias gradients ride on it (the launches that produce the dy operands take them)."""
         n = len(items)
         arr = lambda v: np.array(v, dtype=np.uint64)
         a_dy, a_x = arr([it[0].data_ptr() for it in items]), arr([it[1].data_ptr() for it in items])
         a_dw = arr([it[2].data_ptr() for it in items])
         wires = [self._wire_of(it[2]) for it in items]
         a_16 = arr([w or 0 for w in wires]) if any(wires) else None
-        a_db = arr([(bias[i].data_ptr() if bias and i in bias else 0) for i in range(n)]) if bias else None
         Ns, Ks = np.array([it[3] for it in items], dtype=np.int32), np.array([it[4] for it in items], dtype=np.int32)
         with self._timed(sum(2.0 * Mpad * it[3] * it[4] for it in items), 'bt_group'):
             lib.vitae_wgrad_group_bt(n, a_dy.ctypes.data, a_x.ctypes.data, a_dw.ctypes.data, None if a_16 is None else a_16.ctypes.data,
-                                     None if a_db is None else a_db.ctypes.data, Ns.ctypes.data, Ks.ctypes.data, M, Mpad, int(self._accum),
+                                     None, Ns.ctypes.data, Ks.ctypes.data, M, Mpad, int(self._accum),
                                      self.ws16.data_ptr(), self.ws16.numel(), self.stream)
 
     # ------------------------------------------------------------------ transformer block
     def _block_fwd16(self, pre, q, x_in, x_out, Bs, N, d, heads, hd, hid):
         """model/vit.py:139-144 with bf16 GEMM operands written by their producers."""
         b, p, M = self.buf, self.p, Bs * N
-        q16 = self._qkv16_ok(N, hd)
-        qkv32, qkv16 = (None, b[q + 'qkv_16']) if q16 else (b[q + 'qkv'], None)
         self._ln_fwd(x_in, pre + 'norm1.', None, b[q + 'mean1'], b[q + 'rstd1'], M, d, y16=b[q + 'y1_16'])
-        self._g16_fwd(b[q + 'y1_16'], p[pre + 'attn.qkv.weight'], p[pre + 'attn.qkv.bias'], M, 3 * d, d, y=qkv32, y16=qkv16,
+        self._g16_fwd(b[q + 'y1_16'], p[pre + 'attn.qkv.weight'], p[pre + 'attn.qkv.bias'], M, 3 * d, d, y16=b[q + 'qkv_16'],
                       name=pre + 'attn.qkv.weight')
         with self._timed(4.0 * Bs * heads * N * N * hd, 'attn'):
-            if q16:
-                lib.vitae_sdpa_mfma_fwd_bf16in(_ptr(qkv16), _ptr(b[q + 'o']), _ptr(b[q + 'o_16']), _ptr(b[q + 'lse']), Bs, N, heads, hd,
-                                               self.stream)
-            else:
-                lib.vitae_sdpa_mfma_fwd(_ptr(b[q + 'qkv']), _ptr(b[q + 'o']), _ptr(b[q + 'o_16']), _ptr(b[q + 'lse']), Bs, N, heads, hd,
-                                        self.stream)
+            lib.vitae_sdpa_mfma_fwd_bf16in(_ptr(b[q + 'qkv_16']), _ptr(b[q + 'o']), _ptr(b[q + 'o_16']), _ptr(b[q + 'lse']), Bs, N, heads, hd,
+                                           self.stream)
         self._g16_fwd(b[q + 'o_16'], p[pre + 'attn.proj.weight'], p[pre + 'attn.proj.bias'], M, d, d, y=b[q + 'xmid'], res=x_in,
                       name=pre + 'attn.proj.weight')
         self._ln_fwd(b[q + 'xmid'], pre + 'norm2.', None, b[q + 'mean2'], b[q + 'rstd2'], M, d, y16=b[q + 'y2_16'])
@@ -939,22 +910,10 @@ class HipMAEEngine:
         self._g16_fwd(b[q + 'act_16'], p[pre + 'mlp.fc2.weight'], p[pre + 'mlp.fc2.bias'], M, d, hid, y=x_out, res=b[q + 'xmid'],
                       name=pre + 'mlp.fc2.weight')
 
-    def _qkv16_ok(self, N, hd) -> bool:
-        """bf16-only qkv for this stack: the flag and an MFMA head size (round 3: any sequence length — the two streaming backward
-        kernels read the bf16 copy as well; VITAE_QKV_BF16_LONG=0 keeps fp32 q | k | v when the head does not fit LDS)"""
-        if not (self.qkv16 and hd in (32, 64)):
-            return False
-        return bool(lib.vitae_sdpa_bwd_fused_fits(N, hd) or self.qkv16_long)
-
-    def _dqkv32(self, dqkv, N, hd):
-        """fp32 dqkv is write-only on the bf16-operand path (the qkv weight / input gradients read the bf16 copy): skip it
-        whenever the one-launch attention backward applies (whole head resident in LDS: csrc/attention_mfma.hip answers)."""
-        return None if lib.vitae_sdpa_bwd_fused_fits(N, hd) else dqkv
-
     def _dyset(self, i, Mp, d) -> str:
         """Suffix of the buffer set that holds block i's output-gradient operands (side-stream grouped weight gradients: two
         alternating sets, so that block i's weight-gradient launch may still read its set while block i - 1 runs)."""
-        return '_alt' if (self.wgrad_group_side and (i & 1) and self._grouped(Mp, d)) else ''
+        return '_alt' if ((i & 1) and self._grouped(Mp, d)) else ''
 
     def _block_bwd16(self, pre, q, s, x_in, Bs, N, d, heads, hd, hid, Mp, prev_fc2_bias, idx=0):
         """Backward of one block on bf16 operands.  On entry buf[s+'dx'] (fp32) and buf[s+'dx_16'] hold the
@@ -963,14 +922,14 @@ class HipMAEEngine:
         b, p, g, M = self.buf, self.p, self.g, Bs * N
         self._scope = s
         sfx, sfx_out = self._dyset(idx, Mp, d), self._dyset(idx - 1, Mp, d)
-        dx, dx16, dh16, dy, do, dqkv, dqkv16 = (b[s + 'dx'], b[s + 'dx_16' + sfx], b[s + 'dh_16' + sfx], b[s + 'dy'], b[s + 'do'],
-                                                  b[s + 'dqkv'], b[s + 'dqkv_16' + sfx])
+        dx, dx16, dh16, dy, do, dqkv16 = (b[s + 'dx'], b[s + 'dx_16' + sfx], b[s + 'dh_16' + sfx], b[s + 'dy'], b[s + 'do'],
+                                            b[s + 'dqkv_16' + sfx])
         dx16_out = b[s + 'dx_16' + sfx_out]          # norm1's bf16 result: the output gradient of block idx - 1
         # Many token rows (batch >= ~16, patch 8): the four weight gradients of the block leave as ONE launch at its end
         # (``_wgrad_group``) and the Linears' backward launches compute the input gradients only.  Each dy operand then has to
         # survive until that launch: the gradient w.r.t. the block's middle (norm2's output) goes to a second bf16 buffer.
         grp = self._grouped(Mp, d)
-        side = grp and self.wgrad_group_side and self.gemm_timer is None
+        side = grp and self.gemm_timer is None
         dw = (lambda name: None) if grp else (lambda name: g[name])
         dmid16 = b[s + 'dx_16b' + sfx] if grp else dx16
         if side:
@@ -980,7 +939,7 @@ class HipMAEEngine:
         # input-gradient epilogue it was 128 atomics per 64 x 64 tile: +1.6 / +3.9 us on the 8.7 / 7.4 us launches of the batch-4
         # step (tools/epi_ablate.py, round 5).  Grouped weight gradients (many rows): the big-tile epilogue folds a workgroup's
         # column sums in LDS first.
-        db_w = not grp and self.fc1_bias_by_wgrad
+        db_w = not grp
         self._g16_bwd(dx16, p[pre + 'mlp.fc2.weight'], b[q + 'act_16'], dw(pre + 'mlp.fc2.weight'), M, Mp, d, hid,
                       dx16=dh16, epi=EPI_DGELU | self._aux16, aux=b[q + 'hpre'], dx_colsum=None if db_w else g[pre + 'mlp.fc1.bias'])
         self._g16_bwd(dh16, p[pre + 'mlp.fc1.weight'], b[q + 'y2_16'], dw(pre + 'mlp.fc1.weight'), M, Mp, hid, d, dx=dy,
@@ -991,15 +950,11 @@ class HipMAEEngine:
         # grouped weight gradients: the qkv bias gradient colsum(dqkv) is collected by the attention backward itself (wave
         # shuffles + one atomic per column and workgroup) — as a separate bf16 column-sum launch it was 9-10 us on the main chain of
         # each of the 20 blocks at batch 32 / patch 8
-        qkv_db = g[pre + 'attn.qkv.bias'] if (grp and self.attn_bias_colsum) else None
+        qkv_db = g[pre + 'attn.qkv.bias'] if grp else None
         with self._timed(10.0 * Bs * heads * N * N * hd, 'attn'):
-            if self._qkv16_ok(N, hd):
-                lib.vitae_sdpa_mfma_bwd_bf16in(_ptr(b[q + 'qkv_16']), _ptr(b[q + 'o']), _ptr(do), _ptr(b[q + 'lse']), None, _ptr(dqkv16),
-                                               _ptr(qkv_db), _ptr(b['delta']), Bs, N, heads, hd, self.stream)
-            else:
-                lib.vitae_sdpa_mfma_bwd(_ptr(b[q + 'qkv']), _ptr(b[q + 'o']), _ptr(do), _ptr(b[q + 'lse']), _ptr(self._dqkv32(dqkv, N, hd)),
-                                        _ptr(dqkv16), None, _ptr(b['delta']), Bs, N, heads, hd, self.stream)
-        # the qkv bias gradient colsum(dqkv) rides on the wgrad workgroups (one extra MFMA against a ones operand)
+            lib.vitae_sdpa_mfma_bwd_bf16in(_ptr(b[q + 'qkv_16']), _ptr(b[q + 'o']), _ptr(do), _ptr(b[q + 'lse']), None, _ptr(dqkv16),
+                                           _ptr(qkv_db), _ptr(b['delta']), Bs, N, heads, hd, self.stream)
+        # paired launches: the qkv bias gradient colsum(dqkv) rides on the wgrad workgroups (one extra MFMA against a ones operand)
         self._g16_bwd(dqkv16, p[pre + 'attn.qkv.weight'], b[q + 'y1_16'], dw(pre + 'attn.qkv.weight'), M, Mp, 3 * d, d, dx=dy,
                       dy_colsum=None if grp else g[pre + 'attn.qkv.bias'])
         if grp:       # (before norm1's backward overwrites dx16, the fc2 weight gradient's dy operand)
@@ -1007,16 +962,15 @@ class HipMAEEngine:
                      (dh16, b[q + 'y2_16'], g[pre + 'mlp.fc1.weight'], hid, d),
                      (dmid16, b[q + 'o_16'], g[pre + 'attn.proj.weight'], d, d),
                      (dqkv16, b[q + 'y1_16'], g[pre + 'attn.qkv.weight'], 3 * d, d)]
-            bias = None if (qkv_db is not None and self._qkv16_ok(N, hd)) else {3: g[pre + 'attn.qkv.bias']}
             if side:
                 # beside the chain: its launches leave a third of the CUs idle, and nothing reads these gradients before the phase ends
                 self.wside.wait_stream(torch.cuda.current_stream(self.device))
                 with self._on_branch(self.wside, ws16=self.ws16_wside):
-                    self._wgrad_group(items, M, Mp, bias=bias)
+                    self._wgrad_group(items, M, Mp)
                 self._wg_mark(f'{s}grp{idx & 1}')
                 self._wg_fence(f'{s}grp{(idx + 1) & 1}')    # norm1 writes the OTHER set's dx16, which block idx + 1's launch reads
             else:
-                self._wgrad_group(items, M, Mp, bias=bias)
+                self._wgrad_group(items, M, Mp)
         self._ln_bwd(dy, x_in, pre + 'norm1.', b[q + 'mean1'], b[q + 'rstd1'], dx, M, d, 1, dx16=dx16_out,
                      dx_colsum=prev_fc2_bias)
         self._scope = None
@@ -1104,45 +1058,27 @@ class HipMAEEngine:
             self.flush_hparams()
             lib.vitae_memset_zero(self.acc.data_ptr(), self.acc.numel() * 8, st)
         # --- target branch of the edge loss (blur + Sobel of the input, vit_autoenc.py:221-223) depends on the
-        # data only: it runs on a side stream underneath the encoder/decoder and is joined before the edge MSE
-        main = torch.cuda.current_stream(self.device)
-
-        def target_branch(after=None):
-            if after is not None:
-                self.side.wait_event(after)
-            else:
-                self.side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(self.side):
-                ss = self.side.cuda_stream
-                if self.target_one_pass and lib.vitae_target_edge_supported(C, len(self.taps), Lz, Hy, Wx):
-                    # blur + Sobel of the input in one launch: no blurred intermediates in HBM (csrc/loss_fused.hip)
-                    lib.vitae_target_edge(_ptr(view1), _ptr(b['edge_t']), self._taps_c, len(self.taps), B, C, Lz, Hy, Wx, ss)
-                else:
-                    lib.vitae_gauss_blur_fwd(_ptr(view1), _ptr(b['blur_tmp']), _ptr(b['blurred']), self._taps_c, len(self.taps),
-                                             B * C, Lz, Hy, Wx, ss)
-                    lib.vitae_sobel_edge_fwd(_ptr(b['blurred']), _ptr(b['edge_t']), None, None, B, C, Lz, Hy, Wx, ss)
-
-        # where the branch forks off the main chain: 'start' (beside masking / gather / patch embedding), 'embed' (after the
-        # patch-embedding GEMM, beside the first encoder blocks), 'decoder' (beside the first decoder blocks)
-        fork = self.target_fork
-        # 'start1' (experiment, measured WORSE): the same fork point, but the branch is ENQUEUED after the main chain's next kernel.
-        # In a captured graph the child node created first keeps the parent's hardware queue and the other one pays a ~7-12 us
-        # cross-queue hop; created second, the main chain does stay on its queue (and the patch-embedding GEMM runs 49 instead of
+        # data only: it runs on a side stream underneath the encoder/decoder and is joined before the edge MSE.  It forks off
+        # the main chain HERE, beside masking / gather / patch embedding, and is enqueued before the main chain's next kernel: in a
+        # captured graph the child node created first keeps the parent's hardware queue and the other one pays a ~7-12 us
+        # cross-queue hop; enqueued second, the main chain does stay on its queue (and the patch-embedding GEMM runs 49 instead of
         # 91 us without the blur beside it) — but the graph executor then parks the branch on a queue whose earlier entries wait
         # for the latent: blur + Sobel only start at 1.75 ms, the loss waits for them, the step goes 4.72 -> 4.96 ms
-        fork_ev = None
-        if fork == 'start':
-            target_branch()
-        elif fork == 'start1':
-            fork_ev = torch.cuda.Event()
-            fork_ev.record(main)
+        self.side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.side):
+            ss = self.side.cuda_stream
+            if lib.vitae_target_edge_supported(C, len(self.taps), Lz, Hy, Wx):
+                # blur + Sobel of the input in one launch: no blurred intermediates in HBM (csrc/loss_fused.hip)
+                lib.vitae_target_edge(_ptr(view1), _ptr(b['edge_t']), self._taps_c, len(self.taps), B, C, Lz, Hy, Wx, ss)
+            else:
+                lib.vitae_gauss_blur_fwd(_ptr(view1), _ptr(b['blur_tmp']), _ptr(b['blurred']), self._taps_c, len(self.taps),
+                                         B * C, Lz, Hy, Wx, ss)
+                lib.vitae_sobel_edge_fwd(_ptr(b['blurred']), _ptr(b['edge_t']), None, None, B, C, Lz, Hy, Wx, ss)
         # --- masking, kept-patch gather, patch embedding, sequence assembly
         a16 = self.act16
         pat, pat16 = (None, b['patches_16']) if a16 else (b['patches'], None)
         lib.vitae_random_masking(_ptr(noise), _ptr(b['ids_shuffle']), _ptr(b['ids_restore']), _ptr(b['mask']),
                                  _ptr(b['ids_restore64']), Be, L, keep, st)
-        if fork_ev is not None:
-            target_branch(after=fork_ev)
         if cfg.contrastive:
             lib.vitae_gather_patches_2views(_ptr(view1), _ptr(view2), _ptr(b['ids_shuffle']), _ptr(pat), _ptr(pat16), B, C, Lz, Hy, Wx,
                                             ps, keep, st)
@@ -1152,8 +1088,6 @@ class HipMAEEngine:
             self._g16_fwd(pat16, p['patch_embed.proj.weight'], p['patch_embed.proj.bias'], Be * keep, D, P, y=b['tok'])
         else:
             self._lin_fwd(b['patches'], p['patch_embed.proj.weight'], p['patch_embed.proj.bias'], b['tok'], Be * keep, D, P)
-        if fork == 'embed':
-            target_branch()
         ex = b['encx']
         lib.vitae_encoder_assemble_fwd(_ptr(b['tok']), _ptr(p['cls_token']), _ptr(self.buffers['pos_embed']),
                                        _ptr(b['ids_shuffle']), _ptr(ex[0]), Be, L, keep, D, st)
@@ -1166,8 +1100,6 @@ class HipMAEEngine:
             with self._on_predictor_stream():
                 self._predictor_fwd(training, None)
             self._pred_pending = True
-        if fork == 'decoder':
-            target_branch()
         # --- decoder (view 1 only)
         if a16:
             self._g16_fwd(b['latent_16'], p['decoder_embed.weight'], p['decoder_embed.bias'], B * Ne, Dd, D, y=b['e'], name='decoder_embed.weight')
@@ -1188,7 +1120,7 @@ class HipMAEEngine:
         # --- loss chain on pred = predfull[:, 1:, :]
         pred_ptr, pbs = b['predfull'].data_ptr() + P * 4, Nd * P
         torch.cuda.current_stream(self.device).wait_stream(self.side)   # edge map of the blurred target is ready
-        self._loss_grad_done = bool(loss_with_grad and self.loss_one_pass and lib.vitae_loss_fwd_bwd_supported(C, Lz, Hy, Wx, ps))
+        self._loss_grad_done = bool(loss_with_grad and lib.vitae_loss_fwd_bwd_supported(C, Lz, Hy, Wx, ps))
         if self._loss_grad_done:
             # (bf16 step: the gradient leaves in bf16 only — decoder_pred's dgrad / wgrad read that copy, its bias gradient is the
             # column sum of the same copy)
@@ -1350,7 +1282,6 @@ class HipMAEEngine:
                 # the next phase
                 self._pred0_dgrad()
                 self._pred_joined = True
-            self._ln_flush()
             self._wg_join()
             return
         lib.vitae_decoder_assemble_bwd(_ptr(b['decdx']), _ptr(b['ids_shuffle']), _ptr(b['de']), _ptr(b.get('de_16')),
@@ -1392,7 +1323,6 @@ class HipMAEEngine:
                          dx_colsum=g[f'blocks.{cfg.depth - 1}.mlp.fc2.bias'])
         else:
             self._ln_bwd(b['dlatent'], b['encx'][cfg.depth], 'norm.', b['lat_mean'], b['lat_rstd'], b['encdx'], Me, D, 0)
-        self._ln_flush()
         self._wg_join()
 
     def _pred0_dgrad(self):
@@ -1448,7 +1378,6 @@ class HipMAEEngine:
             else:
                 self._block_bwd(f'blocks.{i}.', f'enc{i}.', 'enc', ex[i], self.Be, self.Ne, cfg.embed_dim, cfg.num_heads,
                                 self.hd, self.Hm)
-        self._ln_flush()
         self._wg_join()
 
     def backward_tail(self):
@@ -1468,7 +1397,7 @@ class HipMAEEngine:
                                     int(self._accum), 1, None, None, self.stream)
         else:
             self._lin_bwd_w(b['dtok'], b['patches'], g['patch_embed.proj.weight'], g['patch_embed.proj.bias'], T, D, P)
-        self._ln_flush(final=True)
+        self._ln_flush()
         self._wg_join()
 
     # ------------------------------------------------------------------ optimiser
@@ -1580,7 +1509,7 @@ class HipMAEEngine:
                     a, e = max(a, s0), min(e, e0)
                     if e > a:
                         lib.vitae_grad_sqnorm(self.grads.data_ptr() + 4 * a, e - a, _ptr(self.acc), None, st)
-                if self.state16 and self.adamw_acc_gate:
+                if self.state16:
                     run = None       # the AdamW launch reads the accumulator itself
                 else:
                     lib.vitae_grad_norm_finalize(_ptr(self.acc), run, st)
@@ -1639,8 +1568,8 @@ class HipMAEEngine:
     # encoder backward is cut into this many phases (= gradient buckets = optimiser-in-backward units)
     # (3: since AdamW got faster a third, smaller last bucket shortens the exposed tail: 5.15 -> 5.00 ms on one box, even on another)
     enc_chunks = int(os.environ.get('VITAE_ENC_CHUNKS', '3'))
-    # loss forward sums + gradient in one pass over the prediction inside the fused step (csrc/loss_fused.hip; 4-channel volumes)
-    loss_one_pass = os.environ.get('VITAE_LOSS_ONE_PASS', '1') != '0'
+    # the fused step's forward left the loss gradient already: loss forward sums + gradient in one pass over the prediction
+    # (csrc/loss_fused.hip, where vitae_loss_fwd_bwd_supported says so)
     _loss_grad_done = False
     # (padded token rows x model width) from which a block's four weight gradients leave as ONE grouped launch.  Measured
     # (volumes/s, grouped vs paired): batch 32 2766 vs 2480, batch 16 1906 vs 1802 (encoder 1792 x 768 grouped: 1906 vs 1843 without),
@@ -1684,10 +1613,8 @@ class HipMAEEngine:
     side, wside, pside, oside = _branch_prop('side'), _branch_prop('wside'), _branch_prop('pside'), _branch_prop('oside')
     del _branch_prop
 
-    adamw_acc_gate = os.environ.get('VITAE_ADAMW_ACC_GATE', '1') != '0'
     wgrad_group_min = int(float(os.environ.get('VITAE_WGRAD_GROUP_MIN', '0.6e6')))
-    bn_split_min_rows = int(os.environ.get('VITAE_BN_SPLIT_MIN_ROWS', '128'))   # predictor BatchNorm: rows per view from which the row-split kernels run
-    target_one_pass = os.environ.get('VITAE_TARGET_ONE_PASS', '1') != '0'
+    bn_split_min_rows = 128   # predictor BatchNorm: rows per view from which the row-split kernels run
     # optional explicit ascending block boundaries, e.g. "0,2,7,12" (uneven chunks: a smaller last, exposed bucket)
     enc_cuts = [int(v) for v in os.environ['VITAE_ENC_CUTS'].split(',')] if os.environ.get('VITAE_ENC_CUTS') else None
 
@@ -1730,9 +1657,7 @@ class HipMAEEngine:
         cfg = self.cfg
         n, nd = self.enc_chunks, self.dec_chunks
         self._epi_norm_on = bool(self.epi_norm and update and self._optimizer_in_backward_ok())
-        if self._epi_norm_on and not self.sq_spread:      # (A/B knob: everything on acc[GRADSQ], the form up to round 5)
-            lib.vitae_gemm_glds_set_wgrad_sqnorm(self.acc.data_ptr() + 8 * _C['VITAE_ACC_GRADSQ'])
-        elif self._epi_norm_on:    # (spread slots: same-address double atomics retire one per ~10 ns — 576 of them per weight-gradient launch)
+        if self._epi_norm_on:      # (spread slots: same-address double atomics retire one per ~10 ns — 576 of them per weight-gradient launch)
             lib.vitae_gemm_glds_set_wgrad_sqnorm_spread(self.acc.data_ptr() + 8 * _C['VITAE_ACC_SQ_BASE'], _C['VITAE_ACC_SQ_SLOTS'],
                                                         _C['VITAE_ACC_SQ_STRIDE'])
         else:

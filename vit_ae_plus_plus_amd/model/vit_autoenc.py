@@ -95,9 +95,7 @@ class _MAEStep(torch.autograd.Function):
         return None, None, None, None, None, None, None
 
 
-_SLOTS = int(os.environ.get('VITAE_INPUT_SLOTS', '2'))     # host batches: 2 = double-buffered on a copy stream, 1 = one slot, 0 = main stream
-_DOUBLE_BUFFER = _SLOTS >= 2
-_MAX_DIRECT = int(os.environ.get('VITAE_DIRECT_GRAPHS', '4'))   # device batches read in place: graphs kept per runner (0 = always stage)
+_MAX_DIRECT = 4   # device batches read in place: graphs kept per runner
 
 
 class _InputSlot:
@@ -131,7 +129,7 @@ class _StepRunner:
     Device batches are staged into a slot in program order (226 MB of HBM traffic, ~0.1 ms of a 5.6 ms step at batch 4)
     — unless the same tensors come back (a dataset that lives in HBM, or the caching allocator handing the loader the
     same blocks again): from the second time on such a batch gets a graph captured on its own addresses and is read in
-    place.  At most ``VITAE_DIRECT_GRAPHS`` of those are kept per runner."""
+    place.  At most ``_MAX_DIRECT`` of those are kept per runner."""
 
     def __init__(self, model, B, mask_ratio, update, accumulate, use_graph):
         self.model, self.eng = model, model._engine
@@ -159,7 +157,7 @@ class _StepRunner:
     def _direct_key(self, view1, view2):
         """Graph key of a device batch that could be read in place, or None (needs the staging copy)."""
         ref = self.st['slots'][0]
-        if not self.use_graph or _MAX_DIRECT <= 0 or (ref.v2 is None) != (view2 is None):
+        if not self.use_graph or (ref.v2 is None) != (view2 is None):
             return None
         for v in (view1,) if view2 is None else (view1, view2):
             if not (v.is_cuda and v.device == ref.v1.device and v.dtype == torch.float32 and v.is_contiguous()
@@ -181,10 +179,10 @@ class _StepRunner:
           0.35 ms in the data-parallel step, so it stays in program order.  ``ready``: kept for callers (no effect)."""
         st = self.st
         main = torch.cuda.current_stream(self.eng.device)
-        host = not view1.is_cuda and (view2 is None or not view2.is_cuda) and _SLOTS >= 1
+        host = not view1.is_cuda and (view2 is None or not view2.is_cuda)
         if host:
             s = st['next']
-            st['cur'], st['next'] = s, (s ^ 1) if _DOUBLE_BUFFER else s
+            st['cur'], st['next'] = s, s ^ 1
             slot, copy = st['slots'][s], st['copy']
             if slot.free is not None:
                 copy.wait_event(slot.free)             # the step that last read this slot is done with it
@@ -515,7 +513,7 @@ class MaskedAutoencoderViT(nn.Module):
         self._set_exchange_buckets(eng, enc_chunks)
         self._reducer = ddp.GradBucketReducer(eng.grads, ddp.engine_bucket_ranges(eng), group=group, force=force,
                                               comm_dtype=comm_dtype)
-        if eng.device.type == 'cuda' and self._reducer.active and os.environ.get('VITAE_DDP_PICK_STREAMS', '1') != '0':
+        if eng.device.type == 'cuda' and self._reducer.active:
             # the all-reduce kernels and the per-bucket AdamW must not share a hardware queue with the backward (or with each
             # other): measured once, here (ddp.pick_streams)
             try:
