@@ -2,7 +2,8 @@
 vitae_linear_bwd_pair_glds (input gradient + weight gradient in ONE launch) with the step's real epilogues — GELU' from the saved
 bf16 derivative on fc2, the bias gradients as row sums in the weight-gradient workgroups, the gradient norm's share — next to the
 same halves as launches of their own.
-    python tools/pair_bench.py [B=4] [iters=20] [model=L128] [tile=5]
+    python tools/pair_bench.py [B=4] [iters=20] [model=L128] [tile=5] [pt=57]
+tile=7: both halves on the wave-specialised 128 x 64 tile; with pt=57 / pt=75 one half stays on 64 x 64 (first digit: the input gradient).
 Prints us per launch (graph replay of `iters` back-to-back launches, 4 operand sets cycled) and the launch's algorithmic TFLOP/s."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -73,7 +74,9 @@ Me, Md = 2 * B * 55, B * 217
 shapes = (('enc', Me, 768, 3072, 12), ('dec', Md, 512, 2048, 8))
 if args.get('model') == 'L128':       # BASELINE config 4: ViT-L/16 on 128^3 volumes (512 patches, 25 % kept + cls; decoder 512 wide on 513 tokens)
     shapes = (('enc', B * 129, 1024, 4096, 24), ('dec', B * 513, 512, 2048, 8))
-if 'tile' in args:                    # force one tile family of the planner (5 = wave-specialised 64 x 64 pair)
+if 'pt' in args:                      # (read per call by vitae_linear_bwd_pair_glds under tile=7)
+    os.environ['VITAE_PAIR_TILES'] = args['pt']
+if 'tile' in args:                    # force one tile family of the planner (5 = wave-specialised 64 x 64 pair, 7 = 128 x 64)
     lib.vitae_gemm_glds_set_bt_tile(int(args['tile']))
 for pre, M, d, h, depth in shapes:
     t = 0.0

@@ -1,7 +1,9 @@
 """Where a wave-specialised 64 x 64 launch spends its time (round 6): s_memtime stamps of consumer wave 0 and producer wave 4 of
 EVERY workgroup of one launch (csrc/gemm_ws64.hip: gemm_ws64_body's `stamp`), for the paired backward launches of the batch-4 step
 and their halves alone.
-    python tools/ws64_phase_probe.py [B=4]
+    python tools/ws64_phase_probe.py [B=4] [tile=7] [only=fc2] [bm1=128]
+tile=7 forces the 128 x 64 tile on both halves (bm1=128 then tells the report where the input gradient's workgroups end); only= keeps
+the cases whose name contains the word.
 Per launch: when workgroups start (dispatch ramp), how long each phase takes (median over workgroups, shader clocks), when the
 last workgroup ends; HIP-event time of the launch alone next to it."""
 import os, sys
@@ -74,7 +76,8 @@ def case(name, M, N, K, gelu=False, dx32=True, dx16=True, dycs=False):
     print(f'--- {name}: M={M} N={N} K={K} (dgrad split {split})')
     t, t0 = report('  pair ', pair)
     # the two halves of the pair separately: dgrad workgroups come first in the launch
-    td = (M + 63) // 64 * ((K + 63) // 64)
+    bm1 = int(args.get('bm1', 64))
+    td = (M + bm1 - 1) // bm1 * ((K + 63) // 64)
     nb1 = (td + 7) // 8 * 8 * split
     clk = 2.4e3
     for nm, part in (('dgrad half', t[:nb1]), ('wgrad half', t[nb1:])):
@@ -90,6 +93,10 @@ def case(name, M, N, K, gelu=False, dx32=True, dx16=True, dycs=False):
 
 
 Me, Md = 2 * B * 55, B * 217
+if 'tile' in args:
+    lib.vitae_gemm_glds_set_bt_tile(int(args['tile']))
+_case = case
+case = lambda name, *a, **k: _case(name, *a, **k) if args.get('only', '') in name else None
 for pre, M, d, h in (('enc', Me, 768, 3072), ('dec', Md, 512, 2048)):
     case(f'{pre} fc2', M, d, h, gelu=True, dx32=False)
     case(f'{pre} fc1', M, h, d, dx16=False, dycs=True)

@@ -253,6 +253,7 @@ bool bt_tile_dims(int id, int& bm, int& bn) {
         case 4: bm = 128; bn = 128; return true;       // wave-specialised (4 MFMA waves + 4 DMA waves, one workgroup per CU)
         case 5: bm = 64; bn = 64; return true;         // ... on a 64 x 64 tile (unsplit launches)
         case 6: bm = 128; bn = 256; return true;       // ... on a 128 x 256 tile, weight-gradient form only
+        case 7: bm = 128; bn = 64; return true;        // ... on a 128 x 64 tile: the 64 x 64 workgroup with two fragments per wave
         default: return false;
     }
 }
@@ -274,7 +275,7 @@ int bt_launch(GArgs p, int a_kc, int b_kc, int id, hipStream_t st) {
     if (id == 6 && (a_kc || b_kc)) return VITAE_ERR_UNSUPPORTED_SHAPE;
     if (id == 0) bt_launch_cfg<256, 256, 2, 4>(p, a_kc, b_kc, st);
     else if (id == 4 || id == 6) ws_launch(p, a_kc, b_kc, id, st);
-    else if (id == 5) ws64_launch(p, a_kc, b_kc, st);
+    else if (id == 5 || id == 7) ws64_launch(p, a_kc, b_kc, id, st);
     else bt_launch_cfg<128, 128, 2, 2>(p, a_kc, b_kc, st);
     return vitae_launch_status();
 }

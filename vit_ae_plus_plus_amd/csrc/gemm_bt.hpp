@@ -1,7 +1,7 @@
 // What the big-tile and wave-specialised bf16 GEMM families share.  One translation unit per family:
 //   gemm_bt.hip     ping-pong 256x256 / 128x128 tiles (ids 0, 3), their grouped weight-gradient kernel, and the dispatchers
 //   gemm_ws.hip     wave-specialised 128x128 / 128x256 tiles (ids 4, 6) and their grouped weight-gradient kernels
-//   gemm_ws64.hip   wave-specialised 64x64 tile (id 5), its two-plane form and the paired dgrad + wgrad launch
+//   gemm_ws64.hip   wave-specialised 64x64 tile (id 5) and 128x64 tile (id 7), the two-plane form and the paired dgrad + wgrad launch
 //   gemm_wsx3.hip   fp32x3 on the 64x64 structure
 //   gemm_ws64q.hip  the paired launch as persistent workgroups
 // Here: the barrier and counted waits of the producer / consumer protocol, the wave-private epilogue and the family's tail
@@ -507,6 +507,6 @@ __device__ __forceinline__ void ws64_consume(const unsigned char* smem, const in
 // p: the descriptor as bt_launch / bt_wgrad_group_launch completed it (k-ranges, tile counts).
 void ws_launch(const GArgs& p, int a_kc, int b_kc, int id /* 4: 128x128, 6: 128x256 (weight-gradient form) */, hipStream_t st);       // gemm_ws.hip
 void ws_wgrad_group_launch(const BtGroup& g, int total, int splits, int kind /* 1: 128x128, 2: 128x256 */, hipStream_t st);             // gemm_ws.hip
-void ws64_launch(const GArgs& p, int a_kc, int b_kc, hipStream_t st);                                                                   // gemm_ws64.hip
+void ws64_launch(const GArgs& p, int a_kc, int b_kc, int id /* 5: 64x64, 7: 128x64 */, hipStream_t st);                                  // gemm_ws64.hip
 
 }  // namespace vglds

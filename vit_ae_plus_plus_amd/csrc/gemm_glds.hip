@@ -665,8 +665,11 @@ inline BtPlan bt_plan(int M, int N, int K, int a_kc, int b_kc, bool allow_split,
     static const double bt_fix1 = getenv("VITAE_BT_FIX1") ? atof(getenv("VITAE_BT_FIX1")) : 4000.0;
     static const double wsw_kt = getenv("VITAE_BT_WSW_KT") ? atof(getenv("VITAE_BT_WSW_KT")) : 1350.0;     // 128 x 256 ws tile (weight-gradient form): 48 KB per k-tile at the CU's 37 B/clk
     static const int wsw_on = getenv("VITAE_BT_WSW") ? atoi(getenv("VITAE_BT_WSW")) : 1;
-    for (int id : {0, 3, 4, 5, 6}) {
+    for (int id : {0, 3, 4, 5, 6, 7}) {
         if (only >= 0 && id != only) continue;
+        // (the 128 x 64 tile, id 7: stand-alone only when forced or asked for by `only` — it lost to the 64 x 64 tile alone on every
+        // input-gradient shape measured; the pair path of vitae_linear_bwd_pair_glds decides for its halves itself)
+        if (id == 7 && g_bt_mode != 7 && only != 7) continue;
         if (id == 6 && (a_kc || b_kc || (g_bt_mode < 0 && !wsw_on))) continue;
         if (id == 5 && g_bt_mode != 5 && (!ws64_on || !allow_ws64)) continue;
         if (g_bt_mode >= 0 && id != g_bt_mode) continue;
@@ -697,6 +700,14 @@ inline BtPlan bt_plan(int M, int N, int K, int a_kc, int b_kc, bool allow_split,
                              : id == 4 ? ws_fix + ((!a_kc && !b_kc) ? ws_kt_w : ws_kt) * nk + (s > 1 ? 6000 + 2200 * s : 0)
                                        : 4500 + 1800 * nk + 7500 + (s > 1 ? bt_fix0 + bt_fix1 * s : 0);
             double clk = rounds * per;
+            if (id == 7) {
+                // wave-specialised 128 x 64 (two workgroups per CU as the 64 x 64 tile): the id-5 term with 24 KB instead of 16 KB per
+                // k-tile (x 1.5) and a longer epilogue per workgroup; not refitted (nothing is planned from it)
+                const double over = wgs > 256 ? (wgs - 256) / 256 : 0, kt = ((!a_kc && !b_kc && wgs >= 512) ? ws64_kt_w : 420) * 1.5;
+                const double lat = (7500 + kt * nk + (s > 1 ? 3000 + 1000 * s : 0)) * (1 + 0.2 * over), thr = wgs * (4000 + kt * nk) / 256;
+                clk = lat > thr ? lat : thr;
+                if (nkt >= 128) clk *= 1.25;
+            }
             if (id == 5) {
                 // wave-specialised 64 x 64: the latency of one workgroup (two share a CU) or, with many, the CUs' L2 -> LDS feed
                 // (fitted to tools/probes/r4_ws64.py / r4_ws64_split.sh: 440 x 768 x 3072 at splits 1 / 2 / 4 / 6 = 16.0 / 12.5 / 11.5 / 14.4 us)
@@ -727,7 +738,7 @@ void launch_pair(int id2, dim3 grid, hipStream_t st, const GArgs& p1, const GArg
 }  // namespace
 
 extern "C" int vitae_gemm_glds_set_bt_tile(int mode) {
-    if (mode < -2 || mode > 6 || mode == 1 || mode == 2) return VITAE_ERR_INVALID_ARG;
+    if (mode < -2 || mode > 7 || mode == 1 || mode == 2) return VITAE_ERR_INVALID_ARG;
     g_bt_mode = mode;
     return VITAE_OK;
 }
@@ -798,7 +809,10 @@ static int gemm_glds_launch(int a_kcontig, int b_kcontig, const void* A16, long 
     p.vec_epi = vec_epilogue_ok(p);
     if (!a_kcontig && !b_kcontig) set_sq(p);      // the weight-gradient form (dy^T @ x)
     if (p.vec_epi) {
-        const BtPlan bp = forced ? *forced : bt_plan(M, N, K, a_kcontig, b_kcontig, epi != VITAE_EPI_GELU);
+        BtPlan bp = forced ? *forced : bt_plan(M, N, K, a_kcontig, b_kcontig, epi != VITAE_EPI_GELU);
+        // (the 128 x 64 tile FORCED: the caller's split, whatever the model would pick — tests and tools run every split of it;
+        // bt_launch refuses what the kernel cannot do)
+        if (!forced && g_bt_mode == 7 && bp.tile == 7) bp.split = split_k;
         if (bp.tile >= 0 && bp.split == split_k) {
             p.splits = split_k;
             return bt_launch(p, a_kcontig, b_kcontig, bp.tile, (hipStream_t)stream);
@@ -967,7 +981,7 @@ extern "C" int vitae_linear_bwd_pair_glds(const void* dy16, const void* w16, con
                                 aux, K, dx_accumulate, sp, splitk_ws, dx_colsum_accum, stream, &pd);
     }
     // both halves as wave-specialised 64 x 64 workgroups of ONE launch (gemm_ws64.hip: gemm_ws64_pair_kernel), the input gradient cut `split` ways
-    auto ws64_pair = [&](int split) -> int {
+    auto ws64_pair = [&](int split, int bm1 = 64, int bm2 = 64) -> int {
         GArgs p1, p2;
         p1.A = reinterpret_cast<const __bf16*>(dy16); p1.lda = N;
         p1.B = reinterpret_cast<const __bf16*>(w16); p1.ldb = K;
@@ -991,14 +1005,45 @@ extern "C" int vitae_linear_bwd_pair_glds(const void* dy16, const void* w16, con
         // one tile per workgroup on the batch-4 / batch-8 pair launches, so it is opt-in; read per call so that a test can switch it)
         const char* wsq_env = getenv("VITAE_WS64Q");
         const int wsq = wsq_env ? atoi(wsq_env) : 0;
-        const int rc = wsq ? ws64q_pair_launch(p1, p2, (hipStream_t)stream) : VITAE_ERR_UNSUPPORTED_SHAPE;
-        return rc != VITAE_ERR_UNSUPPORTED_SHAPE ? rc : ws64_pair_launch(p1, p2, (hipStream_t)stream);
+        const int rc = (wsq && bm1 == 64 && bm2 == 64) ? ws64q_pair_launch(p1, p2, (hipStream_t)stream) : VITAE_ERR_UNSUPPORTED_SHAPE;
+        return rc != VITAE_ERR_UNSUPPORTED_SHAPE ? rc : ws64_pair_launch(p1, p2, (hipStream_t)stream, bm1, bm2);
     };
+    if (g_bt_mode == 7) {
+        // the 128 x 64 tile forced (tests, tools): both halves on it, or, with VITAE_PAIR_TILES=57 / 75 (read per call), one half on the
+        // 64 x 64 tile (first digit: the input gradient's tile id, second: the weight gradient's)
+        const char* pt = getenv("VITAE_PAIR_TILES");
+        const int bm1 = (pt && pt[0] == '5') ? 64 : 128, bm2 = (pt && pt[0] && pt[1] == '5') ? 64 : 128;
+        const BtPlan pd = bt_plan(M, K, N, 1, 0, true, cap);
+        if (pd.tile == 7) {
+            const int rc = ws64_pair(pd.split, bm1, bm2);
+            if (rc != VITAE_ERR_UNSUPPORTED_SHAPE) return rc;
+        }
+    }
     if (g_bt_mode == -1 || g_bt_mode == 5) {
         // Few token rows: the planner puts BOTH halves on that tile
         const BtPlan pd = bt_plan(M, K, N, 1, 0, true, cap), pw = bt_plan(N, K, Mpad, 0, 0, false, cap);
         if (pd.tile == 5 && pw.tile == 5) {
-            const int rc = ws64_pair(pd.split);
+            // Which half runs on 128 x 64 tiles (id 7) is decided for the PAIR, from tools/pair_bench.py at batch 4 and 8 with every
+            // combination forced (profiles/ws128x64_pair_table.txt) and from the launches inside the step (profiles/ws128x64_timeline_b4.txt):
+            //   input gradient: where it is UNSPLIT (with in-launch split-K the 128 x 64 partials double the last arriver's fix-up: alone
+            //     -0.5 ... -2.3 us, inside the step +1.0 / +0.5 / -0.2 us on enc fc1 / enc qkv / dec fc1), the launch has work for about
+            //     a full round of the 512 resident slots (its 64 x 64 workgroups + the weight gradient's >= 448; under that -1.6 ... +1.4)
+            //     and a workgroup's reduction is at most 16 k-tiles (24 / 32 k-tiles on 112 workgroups: 19.1 / 21.0 against 16.1 /
+            //     17.8 us — the launch waits for its longest workgroup);
+            //   weight gradient: only beside such an input gradient (57 is slower than 55 on 12 of 16 shapes), where its 64 x 64 workgroups
+            //     alone nearly fill the slots (>= 384: 432 and 576 gain 0.5-3.4 us; 256 and fewer lose 0.5-1.2 — half as many workgroups
+            //     of twice the length).
+            // The split stays the 64 x 64 plan's.
+            static const int t7_on = getenv("VITAE_PAIR_T7") ? atoi(getenv("VITAE_PAIR_T7")) : 1;
+            int bm1 = 64, bm2 = 64;
+            if (g_bt_mode == -1 && t7_on && pd.split == 1) {
+                const long w5 = (long)cdiv(N, 64) * cdiv(K, 64), d5 = (long)cdiv(M, 64) * cdiv(K, 64);
+                if (N / BK <= 16 && d5 + (w5 >= 384 ? (long)cdiv(N, 128) * cdiv(K, 64) : w5) >= 448) {
+                    bm1 = 128;
+                    if (w5 >= 384) bm2 = 128;
+                }
+            }
+            const int rc = ws64_pair(pd.split, bm1, bm2);
             if (rc != VITAE_ERR_UNSUPPORTED_SHAPE) return rc;
         }
     }

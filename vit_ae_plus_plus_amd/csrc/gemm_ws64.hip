@@ -23,12 +23,19 @@ constexpr int WS64_SMEM = VITAE_WS64_STAGES * 16384;
 // enters at ~2^-17 instead of 2^-9 while the activations stay bf16.  Why: tools/bf16_rounding_ablation.py — the bf16 schedule's
 // loss error against the fp32 reference is carried by the rounding of the WEIGHTS in the forward (1.3e-4 of 1.5e-4 on the total;
 // activations 9e-6, the whole backward 4e-6), and the decoder's fc1 alone is 1.2e-4 of it.
-template <bool A_KC, bool B_KC, int S, bool RS, bool W2 = false>
+// BM = 128 (tile id 7, round 7): the same workgroup on a 128 x 64 tile.  Each consumer wave owns TWO 32 x 32 fragments stacked along M
+// (rows wm * 64 and wm * 64 + 32) that share one B fragment per k-slice; a stage is [A 16 KB | B 8 KB], three stages = 72 KB (the LDS
+// geometry of the W2 form), 0.75x the LDS-fill bytes per flop and half the workgroups of the 64 x 64 tile.  ONE accumulator per
+// fragment (the two fragments are the two independent MFMA chains): with the even / odd pair per fragment the weight-gradient form
+// with row sums needs 64 + 48 (fragments of four k-slices) + 16 registers before any address — over the 128 of two workgroups per CU.
+// So an output element is summed in k order, not in the 64 x 64 tile's even-then-odd order: equal to tile 5 to round-off, not bitwise.
+template <bool A_KC, bool B_KC, int S, bool RS, bool W2 = false, int BM = 64>
 __device__ __forceinline__ void gemm_ws64_body(const GArgs& p, const WsHot& h, const int bid, const int zid, unsigned char* smem) {
 #ifndef VITAE_WS64_PRODUCERS
 #define VITAE_WS64_PRODUCERS 4
 #endif
-    constexpr int BM = 64, BN = 64, NWC = 4, NWP = VITAE_WS64_PRODUCERS;
+    constexpr int BN = 64, NWC = 4, NWP = VITAE_WS64_PRODUCERS, FM = BM / 64;
+    static_assert(BM == 64 || (BM == 128 && !W2), "64 or 128 rows");
     constexpr int A_T = BM * BK * 2, B_T = BN * BK * 2, STG = A_T + (W2 ? 2 : 1) * B_T;
     constexpr int PA = pieces<BM, A_KC, NWP>(), PB = pieces<BN, B_KC, NWP>(), PT = PA + (W2 ? 2 : 1) * PB;
     static_assert(!W2 || (A_KC && B_KC && !RS), "two weight planes: the forward form");
@@ -100,24 +107,49 @@ __device__ __forceinline__ void gemm_ws64_body(const GArgs& p, const WsHot& h, c
     bf16x8 ones;
 #pragma unroll
     for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
-    bf16x8 fa[BK / 16], fb[BK / 16], fb2[W2 ? BK / 16 : 1];
-    constexpr int RK = (A_KC ? 1 : 2) + (W2 ? 2 : 1) * (B_KC ? 1 : 2);
+    bf16x8 fa[FM][BK / 16], fb[BK / 16], fb2[W2 ? BK / 16 : 1];
+    constexpr int RK = FM * (A_KC ? 1 : 2) + (W2 ? 2 : 1) * (B_KC ? 1 : 2);
+    static_assert(2 * RK <= 15, "the counted lgkmcnt of ws64_consume");
+    // BM = 128, row sums: ONE more accumulator for both fragments.  The A fragment goes in as the B operand (same register layout)
+    // against a 0 / 1 selector: rows 0-15 of the result carry the row sums of fragment 0 (column j = row j of A), rows 16-31 those
+    // of fragment 1.
+    bf16x8 sel[2];
+    if constexpr (FM == 2 && RS) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            sel[0][i] = (__bf16)((lane & 16) ? 0.0f : 1.0f);
+            sel[1][i] = (__bf16)((lane & 16) ? 1.0f : 0.0f);
+        }
+    }
     auto rd = [&](const unsigned char* TA, auto kk_c) {
         constexpr int kk = decltype(kk_c)::value;
-        fa[kk] = frag_asm<BM, A_KC>(TA, wm * 32, kk, lane);
+        fa[0][kk] = frag_asm<BM, A_KC>(TA, wm * (BM / 2), kk, lane);
+        if constexpr (FM == 2) fa[1][kk] = frag_asm<BM, A_KC>(TA, wm * (BM / 2) + 32, kk, lane);
         fb[kk] = frag_asm<BN, B_KC>(TA + A_T, wn * 32, kk, lane);
         if constexpr (W2) fb2[kk] = frag_asm<BN, B_KC>(TA + A_T + B_T, wn * 32, kk, lane);
     };
     auto mm = [&](auto kk_c) {
         constexpr int kk = decltype(kk_c)::value;
-        frag_tie(fa[kk]); frag_tie(fb[kk]);
+        if constexpr (FM == 2) {
+            frag_tie(fa[0][kk]); frag_tie(fa[1][kk]); frag_tie(fb[kk]);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][kk], fb[kk], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1][kk], fb[kk], acc[1], 0, 0, 0);
+            if constexpr (RS) {
+                if (rowsum) {
+                    accx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sel[0], fa[0][kk], accx, 0, 0, 0);
+                    accx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sel[1], fa[1][kk], accx, 0, 0, 0);
+                }
+            }
+            return;
+        }
+        frag_tie(fa[0][kk]); frag_tie(fb[kk]);
         if constexpr (W2) {                                              // the small term first
             frag_tie(fb2[kk]);
-            acc[kk & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk], fb2[kk], acc[kk & 1], 0, 0, 0);
+            acc[kk & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][kk], fb2[kk], acc[kk & 1], 0, 0, 0);
         }
-        acc[kk & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk], fb[kk], acc[kk & 1], 0, 0, 0);
+        acc[kk & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][kk], fb[kk], acc[kk & 1], 0, 0, 0);
         if constexpr (RS) {
-            if (rowsum) accx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk], ones, accx, 0, 0, 0);
+            if (rowsum) accx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][kk], ones, accx, 0, 0, 0);
         }
     };
     // the bias of this wave's four-column groups, fetched now (after the loop it would cost an exposed memory latency)
@@ -128,7 +160,15 @@ __device__ __forceinline__ void gemm_ws64_body(const GArgs& p, const WsHot& h, c
     wg_barrier();                                                        // B_0
     stamp(1);
     ws64_consume<2 * RK, S, STG>(smem, nk, rd, mm);
-    if (RS && rowsum && l31 == 0) {
+    if constexpr (FM == 2) {
+        // (lane l of the lower half wave: result rows 0 and 16 — registers 0 and 8 — of column l = the sums of rows l of either fragment)
+        if (RS && rowsum && hi == 0) {
+            const int m = m0 + wm * 64 + l31;
+            if (m < p.M) atomicAdd(p.a_rowsum + m, accx[0]);
+            if (m + 32 < p.M) atomicAdd(p.a_rowsum + m + 32, accx[8]);
+        }
+    }
+    if (FM == 1 && RS && rowsum && l31 == 0) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = m0 + wm * 32 + crow(r, hi);
@@ -139,13 +179,17 @@ __device__ __forceinline__ void gemm_ws64_body(const GArgs& p, const WsHot& h, c
     // either body (pairs of ds_write_b32 merged in the parked quadrant, other compare forms all over the epilogue, other register
     // counts on seven of the ten kernels): written out in both.
     stamp(2);                                                            // k-loop done
-    f32x16 accs[1][1];
+    f32x16 accs[1][FM];
+    if constexpr (FM == 2) {
+        accs[0][0] = acc[0]; accs[0][1] = acc[1];
+    } else {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) accs[0][0][i] = acc[0][i] + acc[1][i];
+        for (int i = 0; i < 16; ++i) accs[0][0][i] = acc[0][i] + acc[1][i];
+    }
     // the epilogue's LDS (4 KB per wave, the split-K flag, the norm shares) ALIASES the stages: every consumer is past its last
     // fragment read at this barrier, every DMA has landed, and the producers are gone — so the whole LDS budget is prefetch depth
     __syncthreads();
-    float* Tw = reinterpret_cast<float*>(smem) + wave * 1024;
+    float* Tw = reinterpret_cast<float*>(smem) + wave * (1024 * FM);
     if (p.splits > 1) {
         // (the producers have left: these barriers count the four consumer waves only)
         const int tile = p.tile0 + tm * p.tiles_n + tn;
@@ -154,49 +198,52 @@ __device__ __forceinline__ void gemm_ws64_body(const GArgs& p, const WsHot& h, c
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         const int toff = (int)threadIdx.x * 16;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 v = {accs[0][0][4 * g], accs[0][0][4 * g + 1], accs[0][0][4 * g + 2], accs[0][0][4 * g + 3]};
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (zid * 4 + g) * (256 * 16) + toff, 0, 16);
+        for (int g = 0; g < 4 * FM; ++g) {
+            const f32x4 v = {accs[0][g >> 2][4 * (g & 3)], accs[0][g >> 2][4 * (g & 3) + 1], accs[0][g >> 2][4 * (g & 3) + 2], accs[0][g >> 2][4 * (g & 3) + 3]};
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (zid * (4 * FM) + g) * (256 * 16) + toff, 0, 16);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        int* flag = reinterpret_cast<int*>(smem + 4 * 4096);
+        int* flag = reinterpret_cast<int*>(smem + 4 * 4096 * FM);
         if (threadIdx.x == 0) *flag = __hip_atomic_fetch_add(reinterpret_cast<int*>(p.ws) + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         stamp(3);                                                        // partials parked, ticket taken
         if (*flag != p.splits - 1) return;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) accs[0][0][i] = 0.f;
-#pragma unroll 1
-        for (int sp0 = 0; sp0 < p.splits; sp0 += 4) {
-            f32x4 v[4][4];
+        for (int f = 0; f < FM; ++f)
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
+            for (int i = 0; i < 16; ++i) accs[0][f][i] = 0.f;
+        constexpr int SU = 4 / FM;                                       // splits in flight together: 16 loads of 16 bytes per lane
+#pragma unroll 1
+        for (int sp0 = 0; sp0 < p.splits; sp0 += SU) {
+            f32x4 v[SU][4 * FM];
+#pragma unroll
+            for (int u = 0; u < SU; ++u) {
                 const int sp = min(sp0 + u, p.splits - 1);               // (clamped: a repeated load, never added)
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    v[u][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (sp * 4 + g) * (256 * 16) + toff, 0, 16));
+                for (int g = 0; g < 4 * FM; ++g)
+                    v[u][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (sp * (4 * FM) + g) * (256 * 16) + toff, 0, 16));
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
+            for (int u = 0; u < SU; ++u)
                 if (sp0 + u < p.splits) {
 #pragma unroll
-                    for (int g = 0; g < 4; ++g)
+                    for (int g = 0; g < 4 * FM; ++g)
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) accs[0][0][4 * g + e] += v[u][g][e];
+                        for (int e = 0; e < 4; ++e) accs[0][g >> 2][4 * (g & 3) + e] += v[u][g][e];
                 }
         }
         if (threadIdx.x == 0) __hip_atomic_store(reinterpret_cast<int*>(p.ws) + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     stamp(4);                                                            // epilogue starts
-    bt_park_quadrant<1, 1, 1>(accs, lane, Tw);
+    bt_park_quadrant<FM, 1, 1>(accs, lane, Tw);
     __builtin_amdgcn_wave_barrier();
     float sqs = 0.f;
-    { f32x4 cz = {0.f, 0.f, 0.f, 0.f}; bt_wave_epilogue<1, 1>(p, bt_epilogue_kind(p), m0 + wm * 32, n0 + wn * 32, Tw, lane, sqs, bias4, cz, false); }
+    { f32x4 cz = {0.f, 0.f, 0.f, 0.f}; bt_wave_epilogue<FM, 1>(p, bt_epilogue_kind(p), m0 + wm * (BM / 2), n0 + wn * 32, Tw, lane, sqs, bias4, cz, false); }
     stamp(5);                                                            // stores issued
     if (p.sqacc) {                                                       // one atomic per workgroup (see bt_tail)
         sqs = wave_sum(sqs);
-        float* red = reinterpret_cast<float*>(smem + 4 * 4096 + 64);
+        float* red = reinterpret_cast<float*>(smem + 4 * 4096 * FM + 64);
         if (lane == 0) red[wave] = sqs;
         __syncthreads();
         if (threadIdx.x == 0) atomicAdd(sq_slot(p), (double)((red[0] + red[1]) + (red[2] + red[3])));
@@ -211,8 +258,24 @@ __global__ __launch_bounds__(64 * (4 + VITAE_WS64_PRODUCERS), 2) void gemm_ws64_
     gemm_ws64_body<A_KC, B_KC, VITAE_WS64_STAGES, false>(p, h, blockIdx.x, blockIdx.z, smem);
 }
 
-void ws64_launch(const GArgs& p, int a_kc, int b_kc, hipStream_t st) {
+// the 128 x 64 tile (id 7): [A 16 KB | B 8 KB] per stage, three stages = 72 KB, two workgroups per CU
+constexpr int WS128X64_STAGES = 3, WS128X64_SMEM = WS128X64_STAGES * 24576;
+template <bool A_KC, bool B_KC>
+__global__ __launch_bounds__(64 * (4 + VITAE_WS64_PRODUCERS), 2) void gemm_ws64_m128_kernel(WS_HOT_PARAMS, const GArgs p) {
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[WS128X64_SMEM];  // the ONLY LDS object
+    const WsHot h{A, B, B2, lda, ldb, M, N, K, (M + 127) >> 7, (N + 63) >> 6, xcd_m, kps};
+    gemm_ws64_body<A_KC, B_KC, WS128X64_STAGES, false, false, 128>(p, h, blockIdx.x, blockIdx.z, smem);
+}
+
+// id: 5 (64 x 64) or 7 (128 x 64); p.tiles_m / p.tiles_n are that tile's counts (bt_launch)
+void ws64_launch(const GArgs& p, int a_kc, int b_kc, int id, hipStream_t st) {
     const dim3 grid(8 * cdiv((long)p.tiles_m * p.tiles_n, 8), 1, p.splits), block(64 * (4 + VITAE_WS64_PRODUCERS));
+    if (id == 7) {
+        if (a_kc && b_kc) hipLaunchKernelGGL((gemm_ws64_m128_kernel<true, true>), grid, block, 0, st, WS_HOT_ARGS(p), p);
+        else if (a_kc && !b_kc) hipLaunchKernelGGL((gemm_ws64_m128_kernel<true, false>), grid, block, 0, st, WS_HOT_ARGS(p), p);
+        else hipLaunchKernelGGL((gemm_ws64_m128_kernel<false, false>), grid, block, 0, st, WS_HOT_ARGS(p), p);
+        return;
+    }
     if (a_kc && b_kc) hipLaunchKernelGGL((gemm_ws64_kernel<true, true>), grid, block, 0, st, WS_HOT_ARGS(p), p);
     else if (a_kc && !b_kc) hipLaunchKernelGGL((gemm_ws64_kernel<true, false>), grid, block, 0, st, WS_HOT_ARGS(p), p);
     else hipLaunchKernelGGL((gemm_ws64_kernel<false, false>), grid, block, 0, st, WS_HOT_ARGS(p), p);
@@ -242,28 +305,46 @@ int ws64_w2_launch(GArgs p, hipStream_t st) {
 // halves of one Linear's backward SHARE dy (A of both), its leading dimension, the leading dimension of W / x, the width K of the layer
 // (N of both), and the weight gradient's rows are the input gradient's reduction length (ws64_pair_launch checks exactly that).
 //   packed = nb1 | p1.splits << 20 | p1.xcd_m << 24 | p2.xcd_m << 25 | (dbg set) << 26
-template <bool RS>
+// BM1 / BM2: the rows of either half's tile (64: tile 5, 128: tile 7), chosen independently; the LDS is the larger need of the two.
+template <bool RS, int BM1, int BM2>
 __global__ __launch_bounds__(64 * (4 + VITAE_WS64_PRODUCERS), 2) void gemm_ws64_pair_kernel(const __bf16* A, const __bf16* B1, const __bf16* B2, int lda, int ldb,
                                                                                            int M1, int N1, int K1, int K2, int kps1, int packed,
                                                                                            const GArgs p1, const GArgs p2) {
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[WS64_SMEM];
+    constexpr int S1 = BM1 == 128 ? WS128X64_STAGES : VITAE_WS64_STAGES, S2 = BM2 == 128 ? WS128X64_STAGES : VITAE_WS64_STAGES;
+    constexpr int SMEM = (BM1 == 128 || BM2 == 128) ? WS128X64_SMEM : WS64_SMEM;
+    static_assert(SMEM >= WS64_SMEM && 2 * SMEM <= 160 * 1024, "either body's stages; two workgroups per CU");
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM];
     const int nb1 = packed & 0xfffff, splits1 = (packed >> 20) & 15, dbg2 = (packed >> 25) & 2;
     if ((int)blockIdx.x < nb1 * splits1) {
-        const WsHot h{A, B1, nullptr, lda, ldb, M1, N1, K1, (M1 + 63) >> 6, (N1 + 63) >> 6, ((packed >> 24) & 1) | dbg2, kps1};
-        gemm_ws64_body<true, false, VITAE_WS64_STAGES, false>(p1, h, blockIdx.x % nb1, blockIdx.x / nb1, smem);
+        const WsHot h{A, B1, nullptr, lda, ldb, M1, N1, K1, (M1 + BM1 - 1) >> (BM1 == 128 ? 7 : 6), (N1 + 63) >> 6, ((packed >> 24) & 1) | dbg2, kps1};
+        gemm_ws64_body<true, false, S1, false, false, BM1>(p1, h, blockIdx.x % nb1, blockIdx.x / nb1, smem);
     } else {
-        const WsHot h{A, B2, nullptr, lda, ldb, K1, N1, K2, (K1 + 63) >> 6, (N1 + 63) >> 6, ((packed >> 25) & 1) | dbg2, K2};
-        gemm_ws64_body<false, false, VITAE_WS64_STAGES, RS>(p2, h, blockIdx.x - nb1 * splits1, 0, smem);
+        const WsHot h{A, B2, nullptr, lda, ldb, K1, N1, K2, (K1 + BM2 - 1) >> (BM2 == 128 ? 7 : 6), (N1 + 63) >> 6, ((packed >> 25) & 1) | dbg2, K2};
+        gemm_ws64_body<false, false, S2, RS, false, BM2>(p2, h, blockIdx.x - nb1 * splits1, 0, smem);
     }
 }
 
-// p1 / p2: complete descriptors of the two halves (vec_epi set, K % 64 == 0); p1.splits k-ranges of >= 2 k-tiles each
-int ws64_pair_launch(GArgs p1, GArgs p2, hipStream_t st) {
+template <bool RS>
+static void ws64_pair_dispatch(int bm1, int bm2, dim3 grid, dim3 block, hipStream_t st, const GArgs& p1, const GArgs& p2, int packed) {
+#define VITAE_WS64_PAIR(B1, B2)                                                                                                              \
+    hipLaunchKernelGGL((gemm_ws64_pair_kernel<RS, B1, B2>), grid, block, 0, st, p1.A, p1.B, p2.B, (int)p1.lda, (int)p1.ldb, p1.M, p1.N, p1.K, \
+                       p2.K, p1.k_per_split, packed, p1, p2)
+    if (bm1 == 64 && bm2 == 64) VITAE_WS64_PAIR(64, 64);
+    else if (bm1 == 64) VITAE_WS64_PAIR(64, 128);
+    else if (bm2 == 64) VITAE_WS64_PAIR(128, 64);
+    else VITAE_WS64_PAIR(128, 128);
+#undef VITAE_WS64_PAIR
+}
+
+// p1 / p2: complete descriptors of the two halves (vec_epi set, K % 64 == 0); p1.splits k-ranges of >= 2 k-tiles each;
+// bm1 / bm2: the rows of either half's tile, 64 (tile 5) or 128 (tile 7)
+int ws64_pair_launch(GArgs p1, GArgs p2, hipStream_t st, int bm1, int bm2) {
+    if ((bm1 != 64 && bm1 != 128) || (bm2 != 64 && bm2 != 128)) return VITAE_ERR_INVALID_ARG;
     if (!p1.vec_epi || !p2.vec_epi || (p1.K % BK) || (p2.K % BK) || p2.K < 2 * BK || p1.a_rowsum) return VITAE_ERR_UNSUPPORTED_SHAPE;
     if (p1.splits < 1) p1.splits = 1;
     if (!bt_k_ranges(p1.K, 2, p1.splits, p1.k_per_split)) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    p1.tiles_m = cdiv(p1.M, 64); p1.tiles_n = cdiv(p1.N, 64); p1.tile0 = 0;
-    p2.tiles_m = cdiv(p2.M, 64); p2.tiles_n = cdiv(p2.N, 64); p2.tile0 = 0;
+    p1.tiles_m = cdiv(p1.M, bm1); p1.tiles_n = cdiv(p1.N, 64); p1.tile0 = 0;
+    p2.tiles_m = cdiv(p2.M, bm2); p2.tiles_n = cdiv(p2.N, 64); p2.tile0 = 0;
     p2.k_per_split = p2.K; p2.splits = 1;
     if (p1.splits > 1 && (!p1.ws || (long)p1.tiles_m * p1.tiles_n > VITAE_GLDS_TICKETS)) return VITAE_ERR_UNSUPPORTED_SHAPE;
     const int nb1 = 8 * cdiv((long)p1.tiles_m * p1.tiles_n, 8), nb2 = 8 * cdiv((long)p2.tiles_m * p2.tiles_n, 8);
@@ -272,10 +353,8 @@ int ws64_pair_launch(GArgs p1, GArgs p2, hipStream_t st) {
     if (p1.A != p2.A || p1.lda != p2.lda || p1.ldb != p2.ldb || p2.M != p1.K || p2.N != p1.N || nb1 >= (1 << 20) || p1.splits > 15 ||
         p1.lda >= (1L << 31) || p1.ldb >= (1L << 31)) return VITAE_ERR_UNSUPPORTED_SHAPE;
     const int packed = nb1 | p1.splits << 20 | (p1.xcd_m & 1) << 24 | (p2.xcd_m & 1) << 25 | ((p1.dbg || p2.dbg) ? 1 << 26 : 0);
-    if (p2.a_rowsum) hipLaunchKernelGGL((gemm_ws64_pair_kernel<true>), grid, block, 0, st, p1.A, p1.B, p2.B, (int)p1.lda, (int)p1.ldb, p1.M, p1.N, p1.K,
-                                        p2.K, p1.k_per_split, packed, p1, p2);
-    else hipLaunchKernelGGL((gemm_ws64_pair_kernel<false>), grid, block, 0, st, p1.A, p1.B, p2.B, (int)p1.lda, (int)p1.ldb, p1.M, p1.N, p1.K,
-                            p2.K, p1.k_per_split, packed, p1, p2);
+    if (p2.a_rowsum) ws64_pair_dispatch<true>(bm1, bm2, grid, block, st, p1, p2, packed);
+    else ws64_pair_dispatch<false>(bm1, bm2, grid, block, st, p1, p2, packed);
     return vitae_launch_status();
 }
 
