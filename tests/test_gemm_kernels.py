@@ -40,8 +40,7 @@ Input families (``family``; properties CPU-tested): plain N(0, 1) — scales: ro
 residual and old C at 1e-3 of the product's scale; there the numerator is the difference to the call without them minus the
 addends, the denominator |bias| + |residual| + |old| alone, so a missing or misplaced addend is of order one.
 
-Which shape reaches which kernel (restated from the launchers; the environment knobs are read once per process and not touched,
-VITAE_WS64Q is read per call and set with monkeypatch):
+Which shape reaches which kernel (restated from the launchers; the environment knobs are not touched):
   vitae_gemm prec 0 / 1, vitae_linear_*   gemm_kernel, 64 x 64 tile, BK = 32, operand extents % 4; split s gives
                         kps = ceil32(ceil(K / s)) and ceil(K / kps) launches in z + splitk_reduce_kernel (GELU: never split).
                         (M, N, K) around (60|64|68, 63|64|65, 4|28|32|36|68|100|132): K = 68 at s = 2 is 64 + 4, K = 100 at
@@ -65,9 +64,9 @@ VITAE_WS64Q is read per call and set with monkeypatch):
                         split under a forced tile is found by scanning K (``k_for_split``): 2 and 3 on tiles 3 - 6.
   vitae_gemm_glds_w2    w2_plan: tile 5 / none -> the two-plane 64 x 64 workgroup (ws64_w2_launch), a forced big tile -> that tile
                         over 2 K with the activations wrapping.
-  vitae_linear_bwd_pair_glds   mode -1, both halves without a big tile -> one gemm_ws64_pair_kernel launch (VITAE_WS64Q=1: the
-                        persistent form where it accepts the shape); mode -2 -> gemm_glds_pair_kernel; forced 3 / 4 / 0 -> two
-                        launches through the planner; dw == NULL -> the input gradient alone.
+  vitae_linear_bwd_pair_glds   mode -1, both halves without a big tile -> one gemm_ws64_pair_kernel launch; mode -2 ->
+                        gemm_glds_pair_kernel; forced 3 / 4 / 0 -> two launches through the planner; dw == NULL -> the input
+                        gradient alone.
   vitae_wgrad_group_bt  kinds by forced tile (-1 planner, 3 ping-pong, 4 / 6 wave-specialised); Mpad >= 256; the split is shrunk
                         to what the workspace holds.
 Every GPU case of family 2 prints ``RATIO`` lines (run with -s); LABNOTES.md keeps the table."""
@@ -1115,14 +1114,11 @@ def pair_exact(lib, C, M, Mpad, N, K, seed=0):
 
 
 @gpu
-@pytest.mark.parametrize('wsq', ['0', '1'])
 @pytest.mark.parametrize('M,Mpad,N,K', [(8, 64, 128, 72), (100, 128, 128, 136), (128, 128, 256, 64), (136, 192, 320, 72), (100, 256, 128, 72)])
-def test_linear_bwd_pair_glds_exact(lib, C, bt_mode, M, Mpad, N, K, wsq, monkeypatch):
+def test_linear_bwd_pair_glds_exact(lib, C, bt_mode, M, Mpad, N, K):
     """the single-launch routes: mode -1 and mode -2 (the 64-row pair kernel) give the same bits, the integer answer; Mpad =
     ceil64(M) and one Mpad = M + 156 (zero rows, then NaN).  Asserted of mode -1: neither half is planned on a big tile (so the
-    two-launch route is out).  ASSUMED, the library has no query for it: that the launch is then gemm_ws64_pair_kernel, and with
-    VITAE_WS64Q=1 its persistent form where ws64q_pair_launch accepts the shape (it falls back to the former otherwise)."""
-    monkeypatch.setenv('VITAE_WS64Q', wsq)
+    two-launch route is out).  ASSUMED, the library has no query for it: that the launch is then gemm_ws64_pair_kernel."""
     dll = lib.load()
     assert dll.vitae_gemm_glds_bt_choice(1, 0, M, K, N) in (5, -1) and dll.vitae_gemm_glds_bt_choice(0, 0, N, K, Mpad) in (5, -1)
     o1 = pair_exact(lib, C, M, Mpad, N, K, seed=M)

@@ -254,3 +254,26 @@ def test_environment_switches_are_the_documented_ones():
     table = re.findall(r'^\| `(VITAE_\w+)` \|', section, flags=re.M)
     assert len(table) == len(set(table)) and len(table) >= 12
     assert set(table) == read, (sorted(read - set(table)), sorted(set(table) - read))
+
+
+def test_library_environment_switches_are_the_documented_ones():
+    """The same for the library: every VITAE_* string literal that csrc/ hands to getenv or to the two helpers of common.hpp (env_int,
+    ENV_INT_ONCE) has a row in DESIGN.md's table of library-side switches, and every row is still read.  Matching on the call keeps
+    VITAE_ERR_* and the other macros out; a name that reaches getenv any other way (a variable, a concatenation) fails the second
+    assertion: the only getenv of csrc/ is the one inside env_int, on its parameter."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, 'vit_ae_plus_plus_amd', 'csrc')
+    read, getenvs = set(), []
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(('.hip', '.hpp')):
+            with open(os.path.join(csrc, f)) as fh:
+                code = re.sub(r'//[^\n]*', '', fh.read())
+            read |= set(re.findall(r'\b(?:getenv|env_int|ENV_INT_ONCE)\(\s*"(VITAE_\w+)"', code))
+            getenvs += [(f, a) for a in re.findall(r'\bgetenv\(\s*([^)]*)\)', code)]
+    assert getenvs == [('common.hpp', 'name')], getenvs
+    with open(os.path.join(root, 'DESIGN.md')) as fh:
+        section = re.search(r'^### 3d-lib\. Library-side switches\n(.*?)^###? ', fh.read(), flags=re.S | re.M).group(1)
+    table = re.findall(r'^\| `(VITAE_\w+)` \|', section, flags=re.M)
+    assert len(table) == len(set(table)) and len(table) >= 15
+    assert set(table) == read, (sorted(read - set(table)), sorted(set(table) - read))

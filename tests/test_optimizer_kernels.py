@@ -20,8 +20,7 @@ bf16-moment entry points: the bounds of test_gpu_ops.test_adamw_bf16_moments (5e
 most 2 % of the stored moments one ulp off, 3e-3 of the update against fp32 moments).  They are exercised at betas = (0.9, 0.95)
 only: bf16 moments need 1 - beta >= 2^-6 (vitae_hip.h), which 0.999 is not.
 
-Sizes reach the code paths (VITAE_ADAMW_* / VITAE_GRADNORM_* are read once per process and are not touched): adamw_kernel runs
-at most 256 workgroups with 8 groups of 4 elements per thread, so groups u >= 1 need n > 262 144, all eight n > 1 835 008 and a
+Sizes reach the code paths: adamw_kernel runs at most 256 workgroups with 8 groups of 4 elements per thread, so groups u >= 1 need n > 262 144, all eight n > 1 835 008 and a
 second loop iteration n > 2 097 152; the norm pass (2048 workgroups) takes a second grid-stride pass above 2 097 152 too.
 
 Every GPU case prints a ``RATIO`` line (run with -s to see them); LABNOTES.md keeps the table."""

@@ -1,7 +1,10 @@
 """Big-tile GEMM family (csrc/gemm_bt.hip): correctness against an fp32 product of the same bf16 operands and GPU time per launch,
 every tile x every operand form, on the shapes of the step at batch 4 / 8 / 32 and on square calibration shapes.
     python tools/bt_bench.py [big] [step] [forms=fwd,dgrad,wgrad] [tiles=0,1,2,3,-2]
-Tile -2 = the 64-row family (the previous default), -1 = the cost model's pick."""
+Tile -2 = the 64-row family (the previous default), -1 = the cost model's pick.
+    python tools/bt_bench.py plan
+launches nothing and needs no GPU: what every planner query of the library answers for the step's problems (all three operand forms)
+and Linear pairs at batch 4 / 8 / 32 — two builds plan alike iff the outputs (one per VITAE_HIP_LIB) are the same bytes."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -25,6 +28,32 @@ def graph_time(go, iters):
         e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1) / iters * 1e3)
     return best
+
+
+def step_shapes(Bt):
+    Me, Md = Bt * 2 * 55, Bt * 217
+    return [('enc qkv', Me, 2304, 768), ('enc proj', Me, 768, 768), ('enc fc1', Me, 3072, 768), ('enc fc2', Me, 768, 3072),
+            ('dec qkv', Md, 1536, 512), ('dec fc1', Md, 2048, 512), ('dec fc2', Md, 512, 2048), ('dec pred', Md, 16384, 512),
+            ('patch embed', Bt * 2 * 54, 768, 16384)]
+
+
+def form_problem(form, M, N, K):
+    return (M, N, K) if form == 'fwd' else (M, K, N) if form == 'dgrad' else (N, K, (M + 63) // 64 * 64)
+
+
+def plan():
+    for Bt in (4, 8, 32):
+        for name, M, N, K in step_shapes(Bt):
+            for form in ('fwd', 'dgrad', 'wgrad'):
+                akc, bkc = {'fwd': (1, 1), 'dgrad': (1, 0), 'wgrad': (0, 0)}[form]
+                m, n, k = form_problem(form, M, N, K)
+                sf = lib.vitae_gemm_glds_pick_split_k_form(akc, bkc, m, n, k)
+                print(f'B{Bt} {name:11s} {form:5s} {m:5d} {n:5d} {k:5d} bt_choice {lib.vitae_gemm_glds_bt_choice(akc, bkc, m, n, k):2d} '
+                      f'split_form {sf} split {lib.vitae_gemm_glds_pick_split_k(m, n, k)} ws_floats {lib.vitae_gemm_glds_ws_floats(m, n, sf)} '
+                      f'wsx3 {lib.vitae_gemm_wsx3_pick_split_k(m, n, k)} bf16 {lib.vitae_gemm_bf16_pick_split_k(m, n, k)} '
+                      f'bf16x3 {lib.vitae_gemm_bf16x3_pick_split_k(m, n, k)}')
+            Mp = (M + 63) // 64 * 64
+            print(f'B{Bt} {name:11s} pair  {M:5d} {Mp:5d} {N:5d} {K:5d} pair_split {lib.vitae_linear_bwd_pair_pick_split_k(M, Mp, N, K)}')
 
 
 def one(form, M, N, K, tile, iters=20, check=True, epi=False):
@@ -73,6 +102,8 @@ def one(form, M, N, K, tile, iters=20, check=True, epi=False):
 
 if __name__ == '__main__':
     args = sys.argv[1:]
+    if 'plan' in args:
+        plan()
     forms = next((a.split('=')[1].split(',') for a in args if a.startswith('forms=')), ['fwd'])
     tiles = next(([int(x) for x in a.split('=')[1].split(',')] for a in args if a.startswith('tiles=')), [0, 3, -2, -1])
     if 'big' in args:
@@ -87,13 +118,9 @@ if __name__ == '__main__':
                     one(form, M, N, K, t, iters=5, epi=True)
     if 'step' in args:
         for Bt in (4, 8, 32):
-            Me, Md = Bt * 2 * 55, Bt * 217
-            shapes = [('enc qkv', Me, 2304, 768), ('enc proj', Me, 768, 768), ('enc fc1', Me, 3072, 768), ('enc fc2', Me, 768, 3072),
-                      ('dec qkv', Md, 1536, 512), ('dec fc1', Md, 2048, 512), ('dec fc2', Md, 512, 2048), ('dec pred', Md, 16384, 512),
-                      ('patch embed', Bt * 2 * 54, 768, 16384)]
-            for name, M, N, K in shapes:
+            for name, M, N, K in step_shapes(Bt):
                 print(f'--- B{Bt} {name}')
                 for form in forms:
-                    m, n, k = (M, N, K) if form == 'fwd' else (M, K, N) if form == 'dgrad' else (N, K, (M + 63) // 64 * 64)
+                    m, n, k = form_problem(form, M, N, K)
                     for t in tiles:
                         one(form, m, n, k, t, iters=20)

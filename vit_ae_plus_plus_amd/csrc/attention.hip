@@ -529,8 +529,7 @@ int launch_bwd_f32mfma(const float* qkv, const float* o, const float* d_o, const
 
 // head sizes the matrix-core kernels serve (VITAE_ATTN_F32_MFMA=0: the VALU kernels everywhere, for A/B timing)
 bool f32mfma_on() {
-    static const bool on = !(getenv("VITAE_ATTN_F32_MFMA") && atoi(getenv("VITAE_ATTN_F32_MFMA")) == 0);
-    return on;
+    return ENV_INT_ONCE("VITAE_ATTN_F32_MFMA", 1) != 0;
 }
 }  // namespace
 

@@ -948,7 +948,7 @@ __global__ __launch_bounds__(256, VITAE_ATTN_FUSED_MINW) void attn_bwd_fused_ker
 // rows (32-row blocks) per wave of the streaming kernels: two blocks halve the LDS fragment reads per MFMA and the workgroup count; one
 // block keeps short sequences spread over more waves.  VITAE_ATTN_RB = 1 / 2 forces it (tools/attn_bench.py).
 static int attn_row_blocks(int N, int head_dim, int which /* 0 fwd, 1 dq, 2 dkv */) {
-    static const int forced = getenv("VITAE_ATTN_RB") ? atoi(getenv("VITAE_ATTN_RB")) : 0;
+    const int forced = ENV_INT_ONCE("VITAE_ATTN_RB", 0);
     if (forced == 1 || forced == 2) return (forced == 2 && head_dim == 64 && which == 2) ? 1 : forced;
     (void)N;
     return 1;   // two blocks per wave (253-256 VGPRs: one wave per SIMD and half the workgroups) measured 177 against 164 us at N = 1729
@@ -961,7 +961,7 @@ static int sdpa_mfma_fwd_launch(const QT* qkv, float* o, void* o_bf16, float* ls
     const float scale = 1.0f / sqrtf((float)head_dim);
     // forward variants (VITAE_ATTN_FWD forces one): 0: 1 query block x 1 key tile per step (short sequences); 1: 1 x 2; 2: 2 x 2
     // (256-key chunks — 1 x 4 and 2 x 2 — measured no faster at N = 1729: 64.0 / 58.7 against 56.9 us; they halve the resident workgroups)
-    static const int forced = getenv("VITAE_ATTN_FWD") ? atoi(getenv("VITAE_ATTN_FWD")) : -1;
+    const int forced = ENV_INT_ONCE("VITAE_ATTN_FWD", -1);
     // (two query blocks per wave also for short sequences once there are enough heads to fill the chip with half the workgroups:
     // batch 32 decoder, N = 217: 22.6 -> 18.6 us; batch 4: 6.7 -> 8.9 us)
     const int var = forced >= 0 ? forced : (N >= 512 ? (head_dim == 32 ? 2 : 1) : (head_dim == 32 && N > 128 && (long)H * B >= 512) ? 2 : 0);
@@ -972,8 +972,7 @@ static int sdpa_mfma_fwd_launch(const QT* qkv, float* o, void* o_bf16, float* ls
 #define VITAE_FWD(HD_, QB_, KT_, CHK_) hipLaunchKernelGGL((attn_fwd_mfma_kernel<HD_, QB_, KT_, CHK_, QT>), grid, dim3(256), 0, st, qkv, o, o16, lse, N, H, scale)
     // (N <= 64 — the encoder of the 96^3 / patch-16 model keeps 55 tokens — takes a 64-key chunk: half the LDS, so three workgroups
     // share a CU instead of two and the 768 heads of a batch-32 step are one round)
-    static const int chk64 = getenv("VITAE_ATTN_FWD_CHK64") ? atoi(getenv("VITAE_ATTN_FWD_CHK64")) : 1;
-    if (var == 0 && N <= 64 && chk64) {
+    if (var == 0 && N <= 64) {
         if (head_dim == 32) VITAE_FWD(32, 1, 1, 64);
         else if (head_dim == 64) VITAE_FWD(64, 1, 1, 64);
         else return VITAE_ERR_UNSUPPORTED_SHAPE;
@@ -1013,7 +1012,7 @@ extern "C" int vitae_sdpa_mfma_fwd_bf16in(const void* qkv_bf16, float* o, void* 
 // one workgroup per head is best — it walks all the head's items, four at a time (batch 32 decoder, 512 heads x 14 items: 42.2 us
 // with two workgroups per head, 31.3 with one); with few heads the items are spread over up to items / 4 workgroups to fill the chip.
 static int fused_bwd_groups(int items, int H, int B) {
-    static const int gforce = getenv("VITAE_ATTN_BWD_G") ? atoi(getenv("VITAE_ATTN_BWD_G")) : 0;
+    const int gforce = ENV_INT_ONCE("VITAE_ATTN_BWD_G", 0);
     if (gforce > 0) return gforce;
     const long heads = (long)H * B;
     int g = cdiv(items, 4), fill = cdiv(512, heads);
@@ -1024,7 +1023,7 @@ static int fused_bwd_groups(int items, int H, int B) {
 // one-launch backward from bf16 q | k | v; VITAE_ERR_UNSUPPORTED_SHAPE when the head does not fit LDS (the caller then keeps an
 // fp32 qkv and uses vitae_sdpa_mfma_bwd).  vitae_sdpa_bwd_fused_fits() answers that up front.
 extern "C" int vitae_sdpa_bwd_fused_fits(int N, int head_dim) {
-    static const int fused_on = getenv("VITAE_ATTN_BWD_FUSED") ? atoi(getenv("VITAE_ATTN_BWD_FUSED")) : 1;
+    const int fused_on = ENV_INT_ONCE("VITAE_ATTN_BWD_FUSED", 1);
     const int NP = cdiv(N, 32) * 32;
     const size_t lds = (size_t)4 * NP * (head_dim + 8) * 2 + (size_t)2 * NP * 4 + (size_t)3 * head_dim * 4;
     return fused_on && (head_dim == 32 || head_dim == 64) && lds <= 150 * 1024;
@@ -1107,7 +1106,7 @@ extern "C" int vitae_sdpa_mfma_bwd(const float* qkv, const float* o, const float
     hipStream_t st = (hipStream_t)stream;
     __bf16* g16 = reinterpret_cast<__bf16*>(dqkv_bf16);
     // whole head resident in LDS -> the one-launch backward
-    static const int fused_on = getenv("VITAE_ATTN_BWD_FUSED") ? atoi(getenv("VITAE_ATTN_BWD_FUSED")) : 1;
+    const int fused_on = ENV_INT_ONCE("VITAE_ATTN_BWD_FUSED", 1);
     const int NP = cdiv(N, 32) * 32;
     const size_t lds = (size_t)4 * NP * (head_dim + 8) * 2 + (size_t)2 * NP * 4 + (size_t)3 * head_dim * 4;
     if (fused_on && (head_dim == 32 || head_dim == 64) && lds <= 150 * 1024) {

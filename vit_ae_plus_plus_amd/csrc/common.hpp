@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define VITAE_OK 0
 #define VITAE_ERR_INVALID_ARG (-1)
@@ -20,6 +21,15 @@ static inline int vitae_launch_status() {
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// The library's environment switches ("Library-side switches"; tests/test_host_logic.py holds that table to the names read
+// here).  env_int: read at every call — for the names a test flips inside one process.  ENV_INT_ONCE: read at the first call of that
+// site and kept for the process.
+static inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+#define ENV_INT_ONCE(name, dflt) ([] { static const int v = env_int(name, dflt); return v; }())
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

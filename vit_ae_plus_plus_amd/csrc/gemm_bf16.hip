@@ -18,7 +18,6 @@
 //  * workgroup ids are remapped so that all M-tiles of one weight panel run on the same XCD (its L2
 //    then serves the panel to the 7-14 workgroups that share it);
 //  * split-K partials go to a workspace and are reduced deterministically (shared with gemm.hip).
-#include <cstdlib>
 #include "common.hpp"
 #include "vitae_hip.h"
 
@@ -179,9 +178,11 @@ __device__ __forceinline__ bf16x8 frag(const __bf16* T, int row0, int kk, int la
     }
 }
 
-// Tile configurations (BM x BN x BK, threads): 64x64x256/256 (default), 64x128x128/256 (large GEMMs),
-// 32x64x256/128 (small GEMMs: twice the workgroups, 2-3 resident per CU so one's MFMA loop overlaps
-// another's load wait).  Waves form a (BM/32) x (rest) grid; wave tile 32 x (32*FN).
+// Tile configurations (BM x BN x BK, threads): 64x64x256/256 (default), 64x128x128/256 (large GEMMs).  Waves form a (BM/32) x (rest)
+// grid; wave tile 32 x (32*FN).
+// NT is 256 in every instantiation that is left (the 128-thread 32x64x256 tile and the 512-thread form of 64x64x256 with KS = 2 wave
+// groups are retired: LABNOTES.md, "Retired library switches").  The parameter, `kh` and the KS reduction below stay as written: hipcc
+// does not fold wave / 4 to zero from the launch bounds, and without them the instruction text of the surviving kernels moves.
 template <int BM, int BN, int BK, int NT, bool A_KC, bool B_KC, bool B_BF16, bool X3 = false> struct TileCfg {
     using SA = Stage<BM, BK, NT, A_KC, false, X3>;
     using SB = Stage<BN, BK, NT, B_KC, B_BF16, X3>;
@@ -328,28 +329,20 @@ void launch(const GemmArgs& p, bool a_kc, bool b_kc, dim3 grid, hipStream_t st) 
 
 }  // namespace
 
-// Tile configuration: cfg 0 = 32x64x256 (128 threads), 1 = 64x64x256, 2 = 64x128x128,
-// 3 = 64x64x256 with 512 threads (two wave groups split each phase's k range: 2 waves per SIMD hide the
-// LDS / MFMA latency of the fragment loop; partial tiles meet in LDS once).
-static inline int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
+// Tile configuration: cfg 1 = 64x64x256, 2 = 64x128x128 once it still yields 512 tiles.
+// (Retired with their kernels, LABNOTES.md "Retired library switches": cfg 0 = 32x64x256 on 128 threads for GEMMs with few tiles,
+// never selected by default; cfg 3 = 64x64x256 on 512 threads, two wave groups splitting each phase's k range — faster on L2-warm
+// operands, slower in the real (cold-weight) step.)
 static inline int pick_cfg(int M, int N) {
-    static const int big = env_int("VITAE_BN128_MIN_TILES", 512), small = env_int("VITAE_BM32_MAX_TILES", 0);
-    static const int w8 = env_int("VITAE_GEMM_8WAVES", 0);   // faster on L2-warm operands, slower in the real (cold-weight) step
-    if (N >= 128 && (long)cdiv(M, 64) * cdiv(N, 128) >= big) return 2;
-    if ((long)cdiv(M, 64) * cdiv(N, 64) < small) return 0;
-    return w8 ? 3 : 1;
+    constexpr int big = 512;
+    return (N >= 128 && (long)cdiv(M, 64) * cdiv(N, 128) >= big) ? 2 : 1;
 }
-static inline int cfg_bm(int c) { return c == 0 ? 32 : 64; }
-static inline int cfg_nt(int c) { return c == 0 ? 128 : (c == 3 ? 512 : 256); }
 static inline int cfg_bn(int c) { return c == 2 ? 128 : 64; }
 static inline int cfg_bk(int c) { return c == 2 ? 128 : 256; }
 
 extern "C" int vitae_gemm_bf16_pick_split_k(int M, int N, int K) {
     const int c = pick_cfg(M, N);
-    const long tiles = (long)cdiv(M, cfg_bm(c)) * cdiv(N, cfg_bn(c));
+    const long tiles = (long)cdiv(M, 64) * cdiv(N, cfg_bn(c));
     if (tiles >= 256 || K < 1024) return 1;
     long s = (512 + tiles - 1) / tiles;
     const long max_by_k = K / 512;   // keep >= 2 phases per split
@@ -377,22 +370,20 @@ extern "C" int vitae_gemm_bf16(int a_kcontig, int b_kcontig, const float* A, lon
     p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc;
     p.M = M; p.N = N; p.K = K;
     const int c = pick_cfg(M, N);
-    const int bm = cfg_bm(c), bn = cfg_bn(c), bk = cfg_bk(c);
+    const int bn = cfg_bn(c), bk = cfg_bk(c);
     int kps = cdiv(cdiv(K, split_k), bk) * bk;
     split_k = cdiv(K, kps);
     if (split_k > 1 && !splitk_ws) return VITAE_ERR_INVALID_ARG;
     p.k_per_split = kps; p.splits = split_k;
     p.bias = bias; p.residual = residual; p.ldr = ldr; p.aux = aux; p.ldaux = ldaux;
     p.epi = epi; p.accumulate = accumulate; p.ws = splitk_ws; p.colsum = a_colsum_accum;
-    p.tiles_m = cdiv(M, bm); p.tiles_n = cdiv(N, bn);
+    p.tiles_m = cdiv(M, 64); p.tiles_n = cdiv(N, bn);
     p.n_per_xcd = cdiv(p.tiles_n, 8);
     dim3 grid(8 * p.n_per_xcd * p.tiles_m, 1, split_k);
     hipStream_t st = (hipStream_t)stream;
     const bool akc = a_kcontig != 0, bkc = b_kcontig != 0;
     if (c == 2) { if (b_is_bf16) launch<64, 128, 128, 256, true>(p, akc, bkc, grid, st); else launch<64, 128, 128, 256, false>(p, akc, bkc, grid, st); }
-    else if (c == 3) { if (b_is_bf16) launch<64, 64, 256, 512, true>(p, akc, bkc, grid, st); else launch<64, 64, 256, 512, false>(p, akc, bkc, grid, st); }
-    else if (c == 1) { if (b_is_bf16) launch<64, 64, 256, 256, true>(p, akc, bkc, grid, st); else launch<64, 64, 256, 256, false>(p, akc, bkc, grid, st); }
-    else { if (b_is_bf16) launch<32, 64, 256, 128, true>(p, akc, bkc, grid, st); else launch<32, 64, 256, 128, false>(p, akc, bkc, grid, st); }
+    else { if (b_is_bf16) launch<64, 64, 256, 256, true>(p, akc, bkc, grid, st); else launch<64, 64, 256, 256, false>(p, akc, bkc, grid, st); }
     if (split_k > 1) {
         const long total = (long)M * N;
         int blocks = (int)((total + 255) / 256);
@@ -406,7 +397,7 @@ extern "C" int vitae_gemm_bf16(int a_kcontig, int b_kcontig, const float* A, lon
 // loads (one phase in flight per workgroup), so a GEMM with fewer workgroups than CUs is cut until it has them (swept in the step:
 // 256 workgroups / 256-deep splits 8.79 ms; 512: 9.27; 768: 9.48; never: 10.38; the bf16 rule of this file: 9.13).
 extern "C" int vitae_gemm_bf16x3_pick_split_k(int M, int N, int K) {
-    static const int want = env_int("VITAE_X3_SPLIT_WGS", 256), min_k = env_int("VITAE_X3_SPLIT_MIN_K", 256);
+    constexpr int want = 256, min_k = 256;
     const long tiles = (long)cdiv(M, 64) * cdiv(N, 64);
     if (tiles >= want || K < 2 * min_k) return 1;
     long s = (want + tiles - 1) / tiles;
@@ -432,9 +423,9 @@ extern "C" int vitae_gemm_bf16x3(int a_kcontig, int b_kcontig, const float* A, l
     if (((uintptr_t)A & 15) || ((uintptr_t)B & 15)) return VITAE_ERR_UNSUPPORTED_SHAPE;
     if (split_k < 1) split_k = 1;
     if ((epi & 15) == VITAE_EPI_GELU) split_k = 1;
-    static const int big = env_int("VITAE_X3_BN128_MIN_TILES", 512), wide_bk = env_int("VITAE_X3_BN128_BK", 64);
+    constexpr int big = 512;
     const bool wide = N >= 128 && (long)cdiv(M, 64) * cdiv(N, 128) >= big;
-    const int bn = wide ? 128 : 64, bk = wide ? wide_bk : 128;   // (64 x 64 x 256 — 135 KB, one workgroup per CU — measured no faster)
+    const int bn = wide ? 128 : 64, bk = wide ? 64 : 128;   // (64 x 64 x 256 — 135 KB, one workgroup per CU — measured no faster)
     GemmArgs p;
     p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc;
     p.M = M; p.N = N; p.K = K;
@@ -450,8 +441,7 @@ extern "C" int vitae_gemm_bf16x3(int a_kcontig, int b_kcontig, const float* A, l
     hipStream_t st = (hipStream_t)stream;
     const bool akc = a_kcontig != 0, bkc = b_kcontig != 0;
     if (!wide) launch<64, 64, 128, 256, false, true>(p, akc, bkc, grid, st);
-    else if (bk == 64) launch<64, 128, 64, 256, false, true>(p, akc, bkc, grid, st);
-    else launch<64, 128, 128, 256, false, true>(p, akc, bkc, grid, st);
+    else launch<64, 128, 64, 256, false, true>(p, akc, bkc, grid, st);
     if (split_k > 1) {
         const long total = (long)M * N;
         int blocks = (int)((total + 255) / 256);
@@ -476,30 +466,24 @@ extern "C" int vitae_linear_bwd_pair_bf16(const float* dy, const void* w_bf16, c
     // dgrad: rows M, cols K (in-features), reduction N
     p1.A = dy; p1.lda = N; p1.B = w_bf16; p1.ldb = K; p1.C = dx; p1.ldc = K;
     p1.M = M; p1.N = K; p1.K = N;
-    int c1 = pick_cfg(M, K), c2 = pick_cfg(N, K);
-    if (cfg_nt(c1) != cfg_nt(c2)) {   // one block size per launch: fall back to the 256-thread shapes
-        if (c1 == 0 || c1 == 3) c1 = 1;
-        if (c2 == 0 || c2 == 3) c2 = 1;
-    }
-    const int bm1 = cfg_bm(c1), bn1 = cfg_bn(c1), bk1 = cfg_bk(c1);
+    const int c1 = pick_cfg(M, K), c2 = pick_cfg(N, K);
+    const int bn1 = cfg_bn(c1), bk1 = cfg_bk(c1);
     p1.k_per_split = cdiv(N, bk1) * bk1; p1.splits = 1;
     p1.bias = nullptr; p1.residual = nullptr; p1.ldr = 0; p1.aux = aux; p1.ldaux = K; p1.epi = epi;
     p1.accumulate = dx_accumulate; p1.ws = nullptr; p1.colsum = db_accum;
-    p1.tiles_m = cdiv(M, bm1); p1.tiles_n = cdiv(K, bn1); p1.n_per_xcd = cdiv(p1.tiles_n, 8);
+    p1.tiles_m = cdiv(M, 64); p1.tiles_n = cdiv(K, bn1); p1.n_per_xcd = cdiv(p1.tiles_n, 8);
     // wgrad: rows N (out-features), cols K, reduction M (tokens)
     p2.A = dy; p2.lda = N; p2.B = x; p2.ldb = K; p2.C = dw; p2.ldc = K;
     p2.M = N; p2.N = K; p2.K = M;
-    const int bm2 = cfg_bm(c2), bn2 = cfg_bn(c2), bk2 = cfg_bk(c2);
+    const int bn2 = cfg_bn(c2), bk2 = cfg_bk(c2);
     p2.k_per_split = cdiv(M, bk2) * bk2; p2.splits = 1;
     p2.bias = nullptr; p2.residual = nullptr; p2.ldr = 0; p2.aux = nullptr; p2.ldaux = 0; p2.epi = VITAE_EPI_NONE;
     p2.accumulate = dw_accumulate; p2.ws = nullptr; p2.colsum = nullptr;
-    p2.tiles_m = cdiv(N, bm2); p2.tiles_n = cdiv(K, bn2); p2.n_per_xcd = cdiv(p2.tiles_n, 8);
+    p2.tiles_m = cdiv(N, 64); p2.tiles_n = cdiv(K, bn2); p2.n_per_xcd = cdiv(p2.tiles_n, 8);
     const int nb1 = 8 * p1.n_per_xcd * p1.tiles_m, nb2 = 8 * p2.n_per_xcd * p2.tiles_m;
     dim3 grid(nb1 + nb2);
     hipStream_t st = (hipStream_t)stream;
-    if (c1 == 0) hipLaunchKernelGGL((gemm_bf16_pair_kernel<128, 32, 64, 256, 32, 64, 256>), grid, dim3(128), 0, st, p1, p2, nb1);
-    else if (c1 == 3) hipLaunchKernelGGL((gemm_bf16_pair_kernel<512, 64, 64, 256, 64, 64, 256>), grid, dim3(512), 0, st, p1, p2, nb1);
-    else if (c1 == 1 && c2 == 1) hipLaunchKernelGGL((gemm_bf16_pair_kernel<256, 64, 64, 256, 64, 64, 256>), grid, dim3(256), 0, st, p1, p2, nb1);
+    if (c1 == 1 && c2 == 1) hipLaunchKernelGGL((gemm_bf16_pair_kernel<256, 64, 64, 256, 64, 64, 256>), grid, dim3(256), 0, st, p1, p2, nb1);
     else if (c1 == 1) hipLaunchKernelGGL((gemm_bf16_pair_kernel<256, 64, 64, 256, 64, 128, 128>), grid, dim3(256), 0, st, p1, p2, nb1);
     else if (c2 == 1) hipLaunchKernelGGL((gemm_bf16_pair_kernel<256, 64, 128, 128, 64, 64, 256>), grid, dim3(256), 0, st, p1, p2, nb1);
     else hipLaunchKernelGGL((gemm_bf16_pair_kernel<256, 64, 128, 128, 64, 128, 128>), grid, dim3(256), 0, st, p1, p2, nb1);

@@ -3,7 +3,6 @@
 //   gemm_ws.hip     wave-specialised 128x128 / 128x256 tiles (ids 4, 6) and their grouped weight-gradient kernels
 //   gemm_ws64.hip   wave-specialised 64x64 tile (id 5) and 128x64 tile (id 7), the two-plane form and the paired dgrad + wgrad launch
 //   gemm_wsx3.hip   fp32x3 on the 64x64 structure
-//   gemm_ws64q.hip  the paired launch as persistent workgroups
 // Here: the barrier and counted waits of the producer / consumer protocol, the wave-private epilogue and the family's tail
 // (bt_tail), the 64x64 consumer loop, the host-side k-range rule, and the per-family launch entry points the dispatchers of
 // gemm_bt.hip call.

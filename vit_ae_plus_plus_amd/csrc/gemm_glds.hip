@@ -564,7 +564,7 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const __bf16* __restri
 
 inline void launch_colsum_bf16(const void* dy16, float* out, int M, int N, hipStream_t st) {
     const int gx = cdiv(N, 256);
-    static const int tgt = getenv("VITAE_COLSUM_BLOCKS") ? atoi(getenv("VITAE_COLSUM_BLOCKS")) : 320;
+    constexpr int tgt = 320;
     int rpw = cdiv(cdiv(M, cdiv(tgt, gx)), 4);
     if (rpw < 4) rpw = 4;
     hipLaunchKernelGGL(colsum_bf16_kernel, dim3(gx, cdiv(M, 4 * rpw)), dim3(256), 0, st, reinterpret_cast<const __bf16*>(dy16), out, M, N, rpw);
@@ -579,17 +579,12 @@ struct Tile { int bm, bn, id; };
 // 8 / splits XCDs — less traffic again, but 5-25 % slower at K <= 3072 and only 3-5 % faster at K = 16384: not kept.)
 // the row-major epilogue moves 4-column groups: every array it touches must be addressable that way
 inline int vec_epilogue_ok(const GArgs& p) {
-    static const int on = getenv("VITAE_GLDS_VEC_EPILOGUE") ? atoi(getenv("VITAE_GLDS_VEC_EPILOGUE")) : 1;
-    if (!on || (p.N & 3)) return 0;
+    if (p.N & 3) return 0;
     auto ok = [](const void* ptr, long ld, int align) { return !ptr || (!(ld & 3) && !((uintptr_t)ptr & (align - 1))); };
     return ok(p.C, p.ldc, 16) && ok(p.C16, p.ldc16, 8) && ok(p.aux, p.ldaux, 16) && ok(p.residual, p.ldr, 16) && ok(p.bias, 0, 16);
 }
 
-inline int xcd_by_rows(int M, int N) {
-    static const int mode = getenv("VITAE_GLDS_XCD_ROWS") ? atoi(getenv("VITAE_GLDS_XCD_ROWS")) : -1;
-    if (mode >= 0) return mode;
-    return M > N;
-}
+inline int xcd_by_rows(int M, int N) { return M > N; }
 
 // 0: 64x64, 1: 64x128 — the wider tile once it still yields enough workgroups for 256 CUs.  (A 128x128 tile inside THIS
 // kernel — 4 waves / 96 KB or 8 waves / 128 KB of LDS, one workgroup per CU — lost to 64x128 on every large GEMM of the step,
@@ -597,7 +592,7 @@ inline int xcd_by_rows(int M, int N) {
 // Round 4, the few-column shapes again with 8 waves / 3 stages and no split: 3520 x 768 x 3072 38.6 us (planner's choice 39.1 in
 // the same cold-operand loop), x 768: 18.1 (14.2), 6944 x 512 x 2048: 32.8 (34.5) — ~1580 clocks per 128 x 128 x 64 k-tile.)
 inline Tile pick_tile(int M, int N) {
-    static const int wide_min = getenv("VITAE_GLDS_WIDE_MIN_TILES") ? atoi(getenv("VITAE_GLDS_WIDE_MIN_TILES")) : 400;
+    constexpr int wide_min = 400;
     if (N >= 128 && (long)cdiv(M, 64) * cdiv(N, 128) >= wide_min) return {64, 128, 1};
     return {64, 64, 0};
 }
@@ -610,13 +605,12 @@ inline Tile pick_tile(int M, int N) {
 //   64-row tiles: throughput bound tiles x (5100 + 400 nk) / 256 (64x64; 2800 + 930 nk for 64x128) or, with few tiles, the
 //   latency of one workgroup 8000 + 760 nk (+ 7000 for the in-launch split-K fix-up).
 // g_bt_mode: -1 the model decides, -2 never, 0 / 3: that tile wherever it is eligible (vitae_gemm_glds_set_bt_tile; VITAE_BT_TILE).
-int g_bt_mode = getenv("VITAE_BT_TILE") ? atoi(getenv("VITAE_BT_TILE")) : -1;
+int g_bt_mode = env_int("VITAE_BT_TILE", -1);
 
 struct BtPlan { int tile, split; double clocks; };
 
 inline int old_split_rule(int M, int N, int K) {
-    static const int min_kt = getenv("VITAE_GLDS_SPLIT_MIN_KT") ? atoi(getenv("VITAE_GLDS_SPLIT_MIN_KT")) : 8;
-    static const int target = getenv("VITAE_GLDS_SPLIT_BLOCKS") ? atoi(getenv("VITAE_GLDS_SPLIT_BLOCKS")) : 384;
+    constexpr int min_kt = 8, target = 384;
     const Tile t = pick_tile(M, N);
     const long tiles = (long)cdiv(M, t.bm) * cdiv(N, t.bn);
     if (tiles >= target / 2 || tiles > VITAE_GLDS_TICKETS) return 1;
@@ -648,37 +642,31 @@ inline BtPlan bt_plan(int M, int N, int K, int a_kc, int b_kc, bool allow_split,
     BtPlan best{-1, 1, 1e30};
     if (g_bt_mode == -2 || K < 2 * BK || (K % BK) || (!a_kc && b_kc) || (N & 3)) return best;
     const int nkt = K / BK;
-    static const int ws_on = getenv("VITAE_BT_WS") ? atoi(getenv("VITAE_BT_WS")) : 1;      // 0: the wave-specialised tile only when forced
-    static const double ws_kt = getenv("VITAE_BT_WS_KT") ? atof(getenv("VITAE_BT_WS_KT")) : 800.0;
-    static const int ws_min_rows = getenv("VITAE_BT_WS_MIN_ROWS") ? atoi(getenv("VITAE_BT_WS_MIN_ROWS")) : 2048;
-    static const int ws_min_rows_fwd = getenv("VITAE_BT_WS_MIN_ROWS_FWD") ? atoi(getenv("VITAE_BT_WS_MIN_ROWS_FWD")) : 800;      // forward launches are never un-paired: batch 16 7.62 -> 7.51 ms, batch 8 neutral
-    static const int ws_long_k = getenv("VITAE_BT_WS_LONG_K") ? atoi(getenv("VITAE_BT_WS_LONG_K")) : 8192;   // ... or a very long reduction (decoder_pred's input gradient, the patch embedding: 37.9 vs 41.7 / 33.8 vs 38.6 us at batch 4)
-    static const double ws_kt_w = getenv("VITAE_BT_WS_KT_W") ? atof(getenv("VITAE_BT_WS_KT_W")) : 900.0;     // both operands row-contiguous (every fragment through two transposing reads; round 5, reads one per MFMA gap: 1280 -> 890 clocks per k-tile)
-    static const double ws_fix = getenv("VITAE_BT_WS_FIX") ? atof(getenv("VITAE_BT_WS_FIX")) : 14000.0;
-    static const int ws64_on = getenv("VITAE_BT_WS64") ? atoi(getenv("VITAE_BT_WS64")) : 1;
+    constexpr double ws_kt = 800.0;
+    constexpr int ws_min_rows = 2048;
+    constexpr int ws_min_rows_fwd = 800;      // forward launches are never un-paired: batch 16 7.62 -> 7.51 ms, batch 8 neutral
+    constexpr int ws_long_k = 8192;           // ... or a very long reduction (decoder_pred's input gradient, the patch embedding: 37.9 vs 41.7 / 33.8 vs 38.6 us at batch 4)
+    constexpr double ws_kt_w = 900.0;         // both operands row-contiguous (every fragment through two transposing reads; round 5, reads one per MFMA gap: 1280 -> 890 clocks per k-tile)
+    constexpr double ws_fix = 14000.0;
+    constexpr double ws64_kt_w = 650.0;
     // in-launch split-K fix-up of the 128 x 128 tile (partials out through write-through stores, ticket, the last arriver's reads):
     // refitted in round 5 — 3072 x 768 x 3520 (weight-gradient form) at split 3 takes 36 us = 86 k clocks, the first fit (6000 + 2200 s)
     // priced it at 58 k and kept the wave-specialised tile (28 us) out; 9000 + 4000 s also keeps 3456 x 768 x 16384 at split 3 (105 us) in front of the ws tile (118)
-    static const double ws64_kt_w = getenv("VITAE_BT_WS64_KT_W") ? atof(getenv("VITAE_BT_WS64_KT_W")) : 650.0;
-    static const int ws_long_any = getenv("VITAE_BT_WS_LONG_ANY") ? atoi(getenv("VITAE_BT_WS_LONG_ANY")) : 1;
-    static const double bt_fix0 = getenv("VITAE_BT_FIX0") ? atof(getenv("VITAE_BT_FIX0")) : 9000.0;
-    static const double bt_fix1 = getenv("VITAE_BT_FIX1") ? atof(getenv("VITAE_BT_FIX1")) : 4000.0;
-    static const double wsw_kt = getenv("VITAE_BT_WSW_KT") ? atof(getenv("VITAE_BT_WSW_KT")) : 1350.0;     // 128 x 256 ws tile (weight-gradient form): 48 KB per k-tile at the CU's 37 B/clk
-    static const int wsw_on = getenv("VITAE_BT_WSW") ? atoi(getenv("VITAE_BT_WSW")) : 1;
+    constexpr double bt_fix0 = 9000.0, bt_fix1 = 4000.0;
+    constexpr double wsw_kt = 1350.0;         // 128 x 256 ws tile (weight-gradient form): 48 KB per k-tile at the CU's 37 B/clk
     for (int id : {0, 3, 4, 5, 6, 7}) {
         if (only >= 0 && id != only) continue;
         // (the 128 x 64 tile, id 7: stand-alone only when forced or asked for by `only` — it lost to the 64 x 64 tile alone on every
         // input-gradient shape measured; the pair path of vitae_linear_bwd_pair_glds decides for its halves itself)
         if (id == 7 && g_bt_mode != 7 && only != 7) continue;
-        if (id == 6 && (a_kc || b_kc || (g_bt_mode < 0 && !wsw_on))) continue;
-        if (id == 5 && g_bt_mode != 5 && (!ws64_on || !allow_ws64)) continue;
+        if (id == 6 && (a_kc || b_kc)) continue;
+        if (id == 5 && g_bt_mode != 5 && !allow_ws64) continue;
         if (g_bt_mode >= 0 && id != g_bt_mode) continue;
-        if (id == 4 && g_bt_mode < 0 && !ws_on) continue;
         // (the wave-specialised tile needs many token rows: at batch 8 — 880 / 1736 rows — it un-pairs launches the 64-row family
         // serves as well and the step loses 7 %)
         // (round 5: a very long reduction qualifies at any row count — decoder_pred's input gradient at batch 8, 1736 x 512 x 16384, ran
         // 76.8 us on 128 x 128 with split 4 against 51.0 here; such launches are never paired anyway)
-        if (id == 4 && g_bt_mode < 0 && (a_kc ? M : K) < ((a_kc && b_kc) ? ws_min_rows_fwd : ws_min_rows) && !(K >= ws_long_k && (ws_long_any || (a_kc ? M : K) < 1024))) continue;
+        if (id == 4 && g_bt_mode < 0 && (a_kc ? M : K) < ((a_kc && b_kc) ? ws_min_rows_fwd : ws_min_rows) && K < ws_long_k) continue;
         if (id == 6 && g_bt_mode < 0 && K < ws_min_rows && K < ws_long_k && (long)M * N < (1L << 22)) continue;      // (as the 128 x 128 ws tile: many token rows only — or a big output: decoder_pred's 16384 x 512 at batch 8, 36 against 41 us)
         int bm, bn;
         bt_tile_dims(id, bm, bn);
@@ -686,7 +674,7 @@ inline BtPlan bt_plan(int M, int N, int K, int a_kc, int b_kc, bool allow_split,
         const bool forced = g_bt_mode >= 0;
         if (!forced && (M < bm / 2 || N < bn / 2)) continue;
         const long tiles = (long)cdiv(M, bm) * cdiv(N, bn);
-        static const int fsplit = getenv("VITAE_BT_SPLIT") ? atoi(getenv("VITAE_BT_SPLIT")) : 0;   // tools: with a forced tile, this split only
+        const int fsplit = ENV_INT_ONCE("VITAE_BT_SPLIT", 0);   // tools: with a forced tile, this split only
         for (int s = 1; s <= (id >= 3 && allow_split ? (id == 6 ? 4 : 8) : 1); ++s) {
             if (forced && fsplit > 0 && s != fsplit) continue;
             const int kps = cdiv(cdiv(K, s), BK) * BK;
@@ -821,7 +809,7 @@ static int gemm_glds_launch(int a_kcontig, int b_kcontig, const void* A16, long 
     if (split_k > 1 && (long)p.tiles_m * p.tiles_n > VITAE_GLDS_TICKETS) return VITAE_ERR_UNSUPPORTED_SHAPE;
     dim3 grid(glds_blocks(p), 1, split_k);
     hipStream_t st = (hipStream_t)stream;
-    static const int pipe_max = getenv("VITAE_GLDS_PIPE_MAX_WGS") ? atoi(getenv("VITAE_GLDS_PIPE_MAX_WGS")) : 512;
+    constexpr int pipe_max = 512;
     if (t.id == 0 && a_kcontig && b_kcontig && (long)grid.x * split_k <= pipe_max) {
         hipLaunchKernelGGL(gemm_glds_pipe_kernel, grid, dim3(256), 0, st, p);
         return vitae_launch_status();
@@ -897,7 +885,7 @@ extern "C" int vitae_gemm_glds_w2(const void* A16, long lda, const void* B16_hil
 extern "C" int vitae_gemm_wsx3_pick_split_k(int M, int N, int K) {
     const long tiles = (long)cdiv(M, 64) * cdiv(N, 64);
     const int nk = cdiv(K, BK);
-    static const int want = getenv("VITAE_X3WS_SPLIT_WGS") ? atoi(getenv("VITAE_X3WS_SPLIT_WGS")) : wsx3_slots() * 7 / 8;
+    static const int want = wsx3_slots() * 7 / 8;
     long s = want / (tiles > 0 ? tiles : 1);
     if (s > 8) s = 8;
     while (s > 1 && nk / s < 4) --s;
@@ -942,8 +930,7 @@ extern "C" int vitae_gemm_wsx3(int a_kcontig, int b_kcontig, const float* A, lon
 extern "C" int vitae_linear_bwd_pair_pick_split_k(int M, int Mpad, int N, int K) {
     // cut the dgrad reduction (N / 64 k-tiles on only ceil(M/64) * K/64 workgroups) down to about the length of the
     // wgrad's (Mpad / 64 k-tiles), which otherwise finishes long before it
-    static const int target = getenv("VITAE_PAIR_SPLIT_TARGET") ? atoi(getenv("VITAE_PAIR_SPLIT_TARGET")) : 10;
-    if (target <= 0) return 1;
+    constexpr int target = 10;
     const int ks1 = N / BK, ks2 = Mpad / BK;
     int s = (ks1 + (ks2 > target ? ks2 : target) / 2) / (ks2 > target ? ks2 : target);
     if (s > 8) s = 8;
@@ -1001,18 +988,13 @@ extern "C" int vitae_linear_bwd_pair_glds(const void* dy16, const void* w16, con
         p2.xcd_m = xcd_by_rows(N, K); p2.tiles_m = 0; p2.tiles_n = 0;
         p2.vec_epi = vec_epilogue_ok(p2);
         if (!p1.vec_epi || !p2.vec_epi) return VITAE_ERR_UNSUPPORTED_SHAPE;
-        // VITAE_WS64Q=1: the persistent form (round 6: csrc/gemm_ws64q.hip gemm_ws64q_pair_kernel — correct, measured 6-10 % SLOWER than
-        // one tile per workgroup on the batch-4 / batch-8 pair launches, so it is opt-in; read per call so that a test can switch it)
-        const char* wsq_env = getenv("VITAE_WS64Q");
-        const int wsq = wsq_env ? atoi(wsq_env) : 0;
-        const int rc = (wsq && bm1 == 64 && bm2 == 64) ? ws64q_pair_launch(p1, p2, (hipStream_t)stream) : VITAE_ERR_UNSUPPORTED_SHAPE;
-        return rc != VITAE_ERR_UNSUPPORTED_SHAPE ? rc : ws64_pair_launch(p1, p2, (hipStream_t)stream, bm1, bm2);
+        return ws64_pair_launch(p1, p2, (hipStream_t)stream, bm1, bm2);
     };
     if (g_bt_mode == 7) {
         // the 128 x 64 tile forced (tests, tools): both halves on it, or, with VITAE_PAIR_TILES=57 / 75 (read per call), one half on the
         // 64 x 64 tile (first digit: the input gradient's tile id, second: the weight gradient's)
-        const char* pt = getenv("VITAE_PAIR_TILES");
-        const int bm1 = (pt && pt[0] == '5') ? 64 : 128, bm2 = (pt && pt[0] && pt[1] == '5') ? 64 : 128;
+        const int pt = env_int("VITAE_PAIR_TILES", 77);
+        const int bm1 = pt / 10 == 5 ? 64 : 128, bm2 = pt % 10 == 5 ? 64 : 128;
         const BtPlan pd = bt_plan(M, K, N, 1, 0, true, cap);
         if (pd.tile == 7) {
             const int rc = ws64_pair(pd.split, bm1, bm2);
@@ -1034,9 +1016,8 @@ extern "C" int vitae_linear_bwd_pair_glds(const void* dy16, const void* w16, con
             //     alone nearly fill the slots (>= 384: 432 and 576 gain 0.5-3.4 us; 256 and fewer lose 0.5-1.2 — half as many workgroups
             //     of twice the length).
             // The split stays the 64 x 64 plan's.
-            static const int t7_on = getenv("VITAE_PAIR_T7") ? atoi(getenv("VITAE_PAIR_T7")) : 1;
             int bm1 = 64, bm2 = 64;
-            if (g_bt_mode == -1 && t7_on && pd.split == 1) {
+            if (g_bt_mode == -1 && pd.split == 1) {
                 const long w5 = (long)cdiv(N, 64) * cdiv(K, 64), d5 = (long)cdiv(M, 64) * cdiv(K, 64);
                 if (N / BK <= 16 && d5 + (w5 >= 384 ? (long)cdiv(N, 128) * cdiv(K, 64) : w5) >= 448) {
                     bm1 = 128;
@@ -1071,8 +1052,7 @@ extern "C" int vitae_linear_bwd_pair_glds(const void* dy16, const void* w16, con
             return vitae_launch_status();
         }
     }
-    static const int pair_ws64_rest = getenv("VITAE_PAIR_WS64_REST") ? atoi(getenv("VITAE_PAIR_WS64_REST")) : 1;
-    if (g_bt_mode == -1 && pair_ws64_rest) {
+    if (g_bt_mode == -1) {
         // Neither the big tiles nor (for both halves) the planner's 64 x 64 choice: what used to fall through to the 64-row pair kernel
         // below.  Round 6, ViT-L/16 on 128^3 (BASELINE config 4, 516 token rows x 1024 / 4096): the wave-specialised pair takes 26.7 /
         // 27.6 us on fc2 / fc1 where that kernel takes 38.3 / 36.7 (tools/pair_bench.py model=L128) — the planner had priced the weight
@@ -1171,16 +1151,14 @@ extern "C" int vitae_wgrad_group_bt(int n, const void* const* dy16, const void* 
         return cdiv(Mpad, kps) == s && kps >= 8 * BK && Mpad - (s - 1) * kps >= 2 * BK && nt <= VITAE_GLDS_TICKETS &&
                VITAE_GLDS_TICKETS + nt * s * area <= cap;
     };
-    static const int env_ws = getenv("VITAE_WGRAD_GROUP_WS") ? atoi(getenv("VITAE_WGRAD_GROUP_WS")) : -1;          // 0 / 1: that kind only
-    const int force_ws = g_bt_mode == 3 ? 0 : g_bt_mode == 4 ? 1 : g_bt_mode == 6 ? 2 : env_ws;                                       // (a forced tile 3 / 4 — tests, tools — forces the kind)
-    static const int force_split = getenv("VITAE_WGRAD_GROUP_SPLIT") ? atoi(getenv("VITAE_WGRAD_GROUP_SPLIT")) : 0;
-    static const double ws_kt = getenv("VITAE_WGRAD_GROUP_WS_KT") ? atof(getenv("VITAE_WGRAD_GROUP_WS_KT")) : 900.0;
-    static const double bt_kt = getenv("VITAE_WGRAD_GROUP_BT_KT") ? atof(getenv("VITAE_WGRAD_GROUP_BT_KT")) : 2650.0;
-    static const double wsw_kt = getenv("VITAE_WGRAD_GROUP_WSW_KT") ? atof(getenv("VITAE_WGRAD_GROUP_WSW_KT")) : 1300.0;
+    const int env_ws = ENV_INT_ONCE("VITAE_WGRAD_GROUP_WS", -1);          // 0 / 1 / 2: that kind only
+    const int force_ws = g_bt_mode == 3 ? 0 : g_bt_mode == 4 ? 1 : g_bt_mode == 6 ? 2 : env_ws;                                       // (a forced tile 3 / 4 / 6 — tests, tools — forces the kind)
+    const int force_split = ENV_INT_ONCE("VITAE_WGRAD_GROUP_SPLIT", 0);
+    constexpr double ws_kt = 900.0, bt_kt = 2650.0, wsw_kt = 1300.0;
     // The wave-specialised kinds are bound by whichever is longer: a CU's own L2 -> LDS rate (900 / 1300 clocks per k-tile of 32 /
     // 48 KB) over its rounds, or the CHIP's — a grouped launch keeps every CU streaming and the eight L2s deliver ~13 TB/s between
     // them (5400 B/clk: tools/wgrad_group_bench.py, encoder block at batch 32: 432 x 55 x 32 KB in 62 us, 216 x 55 x 48 KB in 53).
-    static const double chip_bpc = getenv("VITAE_WGRAD_GROUP_CHIP_BPC") ? atof(getenv("VITAE_WGRAD_GROUP_CHIP_BPC")) : 5400.0;
+    constexpr double chip_bpc = 5400.0;
     int split = 1, ws_tile = 0;
     double best = 1e30;
     for (int kind = 0; kind < 3; ++kind) {

@@ -123,8 +123,6 @@ int bt_wgrad_group_launch(GArgs* ps, int n, int splits, hipStream_t st, int kind
 // gemm_ws64.hip: input gradient + weight gradient of one Linear as ONE launch of wave-specialised workgroups, either half on 64 x 64
 // (tile id 5, bm = 64) or 128 x 64 tiles (id 7, bm = 128)
 int ws64_pair_launch(GArgs p1, GArgs p2, hipStream_t st, int bm1 = 64, int bm2 = 64);
-// gemm_ws64q.hip: the same as persistent workgroups walking a tile queue with the tiles pipelined across each other (round 6)
-int ws64q_pair_launch(GArgs p1, GArgs p2, hipStream_t st);
 // gemm_wsx3.hip: fp32 operands split into bf16 hi + lo by the producer waves of a wave-specialised 64 x 64 workgroup (fp32x3 mode);
 // p.A / p.B point at FLOATS here, p.K any multiple of 4
 int wsx3_launch(GArgs p, int a_kc, int b_kc, hipStream_t st);

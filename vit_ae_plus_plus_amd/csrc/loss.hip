@@ -405,9 +405,9 @@ __device__ __forceinline__ void sobel_mag_tiled_body(const dim3 blockIdx_, const
 }
 
 // Grid-stride forms of the three target-branch kernels (the branch only depends on the input volume and runs on a
-// side stream under the transformer).  VITAE_SIDE_MAX_BLOCKS caps their grids; measured: capping to 256-1024
+// side stream under the transformer).  A cap on their grids was measured: capping to 256-1024
 // workgroups does NOT help the step (5.73-5.78 ms vs 5.69 uncapped) because these kernels are latency-bound per
-// workgroup and slow down more than they give back, so the default is the full virtual grid.
+// workgroup and slow down more than they give back, so the launchers give them the full virtual grid.
 template <int RAD>
 __global__ __launch_bounds__(256) void blur_xy_kernel(const float* __restrict__ in, float* __restrict__ out, int Hy, int Wx,
                                                       int TY, Taps t, int nbx, int total) {
@@ -864,11 +864,6 @@ inline VolGeom make_geom(int C, int Lz, int Hy, int Wx, int p, long pred_bstride
 inline bool bad_extents(int B, int C, int Lz, int Hy, int Wx) { return B <= 0 || C <= 0 || Lz <= 0 || Hy <= 0 || Wx <= 0; }
 inline bool bad_patches(int Lz, int Hy, int Wx, int p) { return p <= 0 || Lz % p || Hy % p || Wx % p; }
 
-inline int side_blocks() {
-    static const int n = getenv("VITAE_SIDE_MAX_BLOCKS") ? atoi(getenv("VITAE_SIDE_MAX_BLOCKS")) : (1 << 30);
-    return n < 1 ? 1 : n;
-}
-
 inline int stream_blocks(long total) {
     long b = (total + 255) / 256;
     return (int)(b > 4096 ? 4096 : b);
@@ -925,11 +920,11 @@ extern "C" int vitae_gauss_blur_fwd(const float* vol, float* tmp, float* out, co
                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
             (void)attr;
         }
-        hipLaunchKernelGGL(blur_xy_kernel<RAD>, dim3(min(tot_xy, side_blocks())), dim3(256), lds, st, vol, tmp, Hy, Wx, TY, t, nbx,
+        hipLaunchKernelGGL(blur_xy_kernel<RAD>, dim3(tot_xy), dim3(256), lds, st, vol, tmp, Hy, Wx, TY, t, nbx,
                            tot_xy);
         const long plane = (long)Hy * Wx;
         const int zx = cdiv(plane, 256), zy = cdiv(Lz, ZC), tot_z = zx * zy * BC;
-        hipLaunchKernelGGL((blur_z_kernel<RAD, ZC>), dim3(min(tot_z, side_blocks())), dim3(256), 0, st, tmp, out, Lz, plane, t, zx, zy,
+        hipLaunchKernelGGL((blur_z_kernel<RAD, ZC>), dim3(tot_z), dim3(256), 0, st, tmp, out, Lz, plane, t, zx, zy,
                            tot_z);
         return vitae_launch_status();
     }
@@ -945,7 +940,7 @@ extern "C" int vitae_sobel_edge_fwd(const float* vol, float* edge, const float* 
     const int xt = cdiv(Wx, TX), yt = cdiv(Hy, TY_), zt = cdiv(Lz, TZ);
     if (zt <= 65535 && B <= 65535) {
         const int tot = xt * yt * zt * B;
-        hipLaunchKernelGGL(sobel_mag_tiled_kernel, dim3(min(tot, side_blocks())), dim3(256), 0, (hipStream_t)stream, vol, edge,
+        hipLaunchKernelGGL(sobel_mag_tiled_kernel, dim3(tot), dim3(256), 0, (hipStream_t)stream, vol, edge,
                            edge_ref, acc, C, Lz, Hy, Wx, xt, xt * yt, zt, tot);
         return vitae_launch_status();
     }
@@ -1004,8 +999,7 @@ extern "C" int vitae_loss_bwd_fused(const float* pred, const float* pred_vol, co
     __bf16* d16 = reinterpret_cast<__bf16*>(dpred_bf16);
     const bool vec_ok = ((uintptr_t)dpred % 16 == 0) && ((uintptr_t)dpred_bf16 % 8 == 0) && pred_bstride % 4 == 0;
     if (zt <= 65535 && B <= 65535 && (C == 1 || (C == 4 && vec_ok))) {
-        static const int row16_on = getenv("VITAE_LOSS_ROW16") ? atoi(getenv("VITAE_LOSS_ROW16")) : 1;
-        const bool row16 = row16_on && Wx % 4 == 0 && ((uintptr_t)pred_vol % 16 == 0);
+        const bool row16 = Wx % 4 == 0 && ((uintptr_t)pred_vol % 16 == 0);
         const dim3 grid(xt * yt, zt, B);
 #define VITAE_LBW(CH_, R_) hipLaunchKernelGGL((loss_bwd_fused_kernel<CH_, R_>), grid, dim3(256), 0, st, pred_vol, imgs, mask, edge_pred, \
                                               edge_tgt, hp, dpred, d16, nonfinite_flag, inv_count, inv_pm, xt, g)

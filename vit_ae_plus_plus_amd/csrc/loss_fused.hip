@@ -62,11 +62,10 @@ __device__ __forceinline__ bool piece_of(const Pieces& pc, int& xt, int& yseg, i
     ztile = id % pc.zt; b = id / pc.zt;
     return true;
 }
-// (the knob is read at EVERY launch on purpose — tests/test_gpu_ops.py flips it inside one process to show the results do not
-// depend on the map; a getenv is ~0.1 us of host time per launch.  The 8 is the XCD count of the one chip this library is built for.)
-inline Pieces make_pieces(int xtiles, int nseg, int zt, int B, const char* env, unsigned& grid) {
-    const char* e = getenv(env);
-    const int on = e ? atoi(e) : 1;
+// (on: the launcher's switch, VITAE_LOSS_XCD / VITAE_TARGET_XCD, read at EVERY launch on purpose — tests/test_gpu_ops.py flips it inside
+// one process to show the results do not depend on the map; a getenv is ~0.1 us of host time per launch.  The 8 is the XCD count of
+// the one chip this library is built for.)
+inline Pieces make_pieces(int xtiles, int nseg, int zt, int B, int on, unsigned& grid) {
     Pieces pc;
     pc.xtiles = xtiles; pc.nseg = nseg; pc.zt = zt;
     pc.n = xtiles * nseg * zt * B;
@@ -517,7 +516,7 @@ extern "C" int vitae_loss_fwd_bwd(const float* pred, long pred_bstride, const fl
     const int zt = cdiv(Lz, NW - 2);
     // y-segments: one workgroup per CU is enough (measured: 124 us with 256 workgroups, 145 with 1024 at batch 4 — every segment
     // re-does 4 rows of the march); rows per segment a multiple of 4 and at least 8
-    static const int target = getenv("VITAE_LOSS_WGS") ? atoi(getenv("VITAE_LOSS_WGS")) : 256;
+    constexpr int target = 256;
     int nseg = cdiv(target, g.xtiles * zt * B);
     if (nseg < 1) nseg = 1;
     int tys = cdiv(cdiv(Hy, nseg), 4) * 4;
@@ -528,7 +527,7 @@ extern "C" int vitae_loss_fwd_bwd(const float* pred, long pred_bstride, const fl
     g.inv_count = 1.0f / (float)((long)B * g.V);
     g.inv_pm = 1.0f / ((float)g.P * mask_sum);
     unsigned grid;
-    g.pc = make_pieces(g.xtiles, nseg, zt, B, "VITAE_LOSS_XCD", grid);
+    g.pc = make_pieces(g.xtiles, nseg, zt, B, env_int("VITAE_LOSS_XCD", 1), grid);
     if (dpred)
         hipLaunchKernelGGL(loss_fwd_bwd_kernel<true>, dim3(grid), dim3(NT), 0, (hipStream_t)stream, pred, imgs, mask, edge_tgt,
                            hp, dpred, reinterpret_cast<__bf16*>(dpred_bf16), nonfinite_flag, acc, g);
@@ -552,7 +551,7 @@ extern "C" int vitae_target_edge(const float* imgs, float* edge_tgt, const float
     for (int i = 0; i < TAPS; ++i) g.k[i] = taps_host[i];
     g.xtiles = cdiv(Wx, XO_T); g.xo = cdiv(Wx, g.xtiles);
     const int zt = cdiv(Lz, NW - 2);
-    static const int target = getenv("VITAE_TARGET_WGS") ? atoi(getenv("VITAE_TARGET_WGS")) : 256;
+    constexpr int target = 256;
     int nseg = cdiv(target, g.xtiles * zt * B);
     if (nseg < 1) nseg = 1;
     int tys = cdiv(cdiv(Hy, nseg), 4) * 4;                 // (every segment re-does 12 rows of the march)
@@ -561,7 +560,7 @@ extern "C" int vitae_target_edge(const float* imgs, float* edge_tgt, const float
     g.tys = tys;
     nseg = cdiv(Hy, tys);
     unsigned grid;
-    g.pc = make_pieces(g.xtiles, nseg, zt, B, "VITAE_TARGET_XCD", grid);
+    g.pc = make_pieces(g.xtiles, nseg, zt, B, env_int("VITAE_TARGET_XCD", 1), grid);
     hipLaunchKernelGGL(target_edge_kernel, dim3(grid), dim3(NT), 0, (hipStream_t)stream, imgs, edge_tgt, g);
     return vitae_launch_status();
 }

@@ -989,7 +989,7 @@ extern "C" int vitae_layernorm_fwd(const float* x, const float* w, const float* 
     if (!x || !w || !b || (!y && !y_bf16) || !mean || !rstd || M <= 0 || D <= 0) return VITAE_ERR_INVALID_ARG;
     if (D > 64 * LN_MAX_PER_LANE) return VITAE_ERR_UNSUPPORTED_SHAPE;
     __bf16* y16 = reinterpret_cast<__bf16*>(y_bf16);
-    static const int vec_on = getenv("VITAE_LN_VEC") ? atoi(getenv("VITAE_LN_VEC")) : 1;     // 0: 4-byte accesses (A/B)
+    const int vec_on = ENV_INT_ONCE("VITAE_LN_VEC", 1);     // 0: 4-byte accesses (A/B)
     const bool aligned = vec_on && !(((uintptr_t)x | (uintptr_t)w | (uintptr_t)b | (uintptr_t)y) & 15) && !((uintptr_t)y16 & 7);
     hipStream_t st = (hipStream_t)stream;
     if (aligned && D == 768) hipLaunchKernelGGL(layernorm_fwd_vec_kernel<3>, dim3(cdiv(M, 4)), dim3(256), 0, st, x, M, eps, w, b, y, y16, mean, rstd);
@@ -1006,12 +1006,12 @@ extern "C" int vitae_layernorm_bwd(const float* dy, const float* x, const float*
     if (!dy || !x || !w || !mean || !rstd || !dx || !dw || !db || M <= 0 || D <= 0) return VITAE_ERR_INVALID_ARG;
     if (D > 64 * LN_MAX_PER_LANE) return VITAE_ERR_UNSUPPORTED_SHAPE;
     __bf16* dx16v = reinterpret_cast<__bf16*>(dx_bf16);
-    static const int vec_on = getenv("VITAE_LN_VEC") ? atoi(getenv("VITAE_LN_VEC")) : 1;
+    const int vec_on = ENV_INT_ONCE("VITAE_LN_VEC", 1);
     const bool aligned = vec_on && !(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)w | (uintptr_t)dx) & 15) && !((uintptr_t)dx16v & 7);
     if (aligned && (D == 768 || D == 512 || D == 256)) {
         const size_t lds = (size_t)12 * D * sizeof(float);
         hipStream_t st = (hipStream_t)stream;
-        static const int cap = getenv("VITAE_LN_BWD_BLOCKS") ? atoi(getenv("VITAE_LN_BWD_BLOCKS")) : 128;   // (sweep: 64 / 128 / 192 / 256 / 512 / all -> 18.3 / 13.0 / 13.3 / 13.1 / 18.1 / 18.6 us at M = 3520, D = 768; 8.2 / 7.5 / 8.8 / 9.8 / 9.5 / 9.5 at M = 1736, D = 512)
+        const int cap = ENV_INT_ONCE("VITAE_LN_BWD_BLOCKS", 128);   // (sweep: 64 / 128 / 192 / 256 / 512 / all -> 18.3 / 13.0 / 13.3 / 13.1 / 18.1 / 18.6 us at M = 3520, D = 768; 8.2 / 7.5 / 8.8 / 9.8 / 9.5 / 9.5 at M = 1736, D = 512)
         const int nb = min(cdiv(M, 8), cap < 1 ? 1 : cap);
         if (D == 768) hipLaunchKernelGGL((layernorm_bwd_rows_vec_kernel<2, 3>), dim3(nb), dim3(256), lds, st, dy, x, w, mean, rstd, dx, dw, db, dx16v, dx_colsum_accum, M, dx_accumulate);
         else if (D == 512) hipLaunchKernelGGL((layernorm_bwd_rows_vec_kernel<2, 2>), dim3(nb), dim3(256), lds, st, dy, x, w, mean, rstd, dx, dw, db, dx16v, dx_colsum_accum, M, dx_accumulate);
@@ -1033,7 +1033,7 @@ extern "C" int vitae_layernorm_bwd(const float* dy, const float* x, const float*
 
 // workgroups (= partial records) of vitae_layernorm_bwd_part for M rows
 extern "C" int vitae_layernorm_bwd_part_records(int M) {
-    static const int cap = getenv("VITAE_LN_PART_BLOCKS") ? atoi(getenv("VITAE_LN_PART_BLOCKS")) : 256;   // (128 / 256 / 512 workgroups at [3464, 768]: 12.5 / 10.0 / 9.5 us, but the reduce reads 1.2 / 2.3 / 4.1 MB per LayerNorm: 0.6 / 1.4 / 2.4 us)
+    const int cap = ENV_INT_ONCE("VITAE_LN_PART_BLOCKS", 256);   // (128 / 256 / 512 workgroups at [3464, 768]: 12.5 / 10.0 / 9.5 us, but the reduce reads 1.2 / 2.3 / 4.1 MB per LayerNorm: 0.6 / 1.4 / 2.4 us)
     const int ng = cdiv(M, 8);
     return ng < cap ? ng : cap;
 }

@@ -480,7 +480,7 @@ template <typename G>
 static int grad_sqnorm_launch(const G* grads, long n, double* acc, float* norm_out, void* stream) {
     if (!grads || !acc || n <= 0 || ((uintptr_t)grads & 15)) return VITAE_ERR_INVALID_ARG;
     long blocks = (n / 4 + 255) / 256;
-    static const long maxg = getenv("VITAE_GRADNORM_MAX_BLOCKS") ? atol(getenv("VITAE_GRADNORM_MAX_BLOCKS")) : 2048;
+    constexpr long maxg = 2048;
     if (blocks > maxg) blocks = maxg;
     if (blocks < 1) blocks = 1;
     hipStream_t st = (hipStream_t)stream;
@@ -512,26 +512,16 @@ static int adamw_launch(float* params, const G* grads, S* exp_avg, S* exp_avg_sq
     long blocks = (n / 4 + 255) / 256;
     // one 256-thread workgroup per CU: as fast alone as any larger grid (5.4-5.7 TB/s) and it leaves the CUs' other wave
     // slots to the backward kernels this pass runs beside (in-backward optimiser); fewer workgroups lose bandwidth
-    static const long maxb = getenv("VITAE_ADAMW_MAX_BLOCKS") ? atol(getenv("VITAE_ADAMW_MAX_BLOCKS")) : 256;
+    constexpr long maxb = 256;
     if (blocks > maxb) blocks = maxb;
     if (blocks < 1) blocks = 1;
     // 30 B/element of HBM traffic; 5.0-5.7 TB/s for every grid size >= 256 workgroups and cache policy tried (the
     // read-only grad-norm pass reaches 5.4 TB/s on the same box), i.e. this kernel sits at the achievable HBM rate.
     // groups in flight per thread: 2 -> 8 took the pass from 5.0 to 6.1 TB/s alone and the step from 5.58 to 5.18 ms (it
     // spends less time beside the backward kernels it slows down); 12 and 16 are slower again (5.21 / 5.32 ms)
-    static const int unroll = getenv("VITAE_ADAMW_UNROLL") ? atoi(getenv("VITAE_ADAMW_UNROLL")) : 8;
-    if (unroll == 4)
-        hipLaunchKernelGGL((adamw_kernel<true, G, 4, S>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
-                           exp_avg_sq, reinterpret_cast<__bf16*>(shadow_bf16), n, hp, grad_norm, weight_decay, gacc);
-    else if (unroll == 12)
-        hipLaunchKernelGGL((adamw_kernel<true, G, 12, S>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
-                           exp_avg_sq, reinterpret_cast<__bf16*>(shadow_bf16), n, hp, grad_norm, weight_decay, gacc);
-    else if (unroll == 8)
-        hipLaunchKernelGGL((adamw_kernel<true, G, 8, S>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
-                           exp_avg_sq, reinterpret_cast<__bf16*>(shadow_bf16), n, hp, grad_norm, weight_decay, gacc);
-    else
-        hipLaunchKernelGGL((adamw_kernel<true, G, 2, S>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
-                           exp_avg_sq, reinterpret_cast<__bf16*>(shadow_bf16), n, hp, grad_norm, weight_decay, gacc);
+    constexpr int unroll = 8;
+    hipLaunchKernelGGL((adamw_kernel<true, G, unroll, S>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                       exp_avg_sq, reinterpret_cast<__bf16*>(shadow_bf16), n, hp, grad_norm, weight_decay, gacc);
     return vitae_launch_status();
 }
 
