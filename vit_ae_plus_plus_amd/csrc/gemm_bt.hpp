@@ -226,27 +226,52 @@ __device__ __forceinline__ int bt_epilogue_kind(const GArgs& p) {
     return p.epi == VITAE_EPI_GELU ? 3 : p.epi == VITAE_EPI_DGELU ? 4 : p.epi == VITAE_EPI_RELU_MASK ? 5 : p.epi == VITAE_EPI_RELU ? 6 : 7;
 }
 
+// Which of the specialised instantiations above a kernel carries (KINDS of bt_wave_epilogue): bit k = kind k (0 - 6; for 3 / 4 / 5
+// with an fp32 aux), bit 8 + k = kind k with a bf16 aux (3 / 4 / 5).  Kind 7 is in every set and takes whatever the set leaves out:
+// a caller outside a kernel's set gets the same result from the run-time-checked path, only slower.  One instantiation is 5-6 KB
+// of code on a 32 x 32 part and 10-12 KB on a 64 x 32 part, a workgroup runs ONE of them, and the full set was 125 of the 132 KB of a
+// 64 x 64 kernel: the sets below are what the library's callers launch in each operand form.
+constexpr int bt_kind(int k) { return 1 << k; }
+constexpr int bt_kind16(int k) { return 1 << (8 + k); }
+constexpr int BT_KINDS_ALL = 0x7f | bt_kind16(3) | bt_kind16(4) | bt_kind16(5);
+// forward form (x W^T): everything but the two epilogues that read what a forward saved
+constexpr int BT_KINDS_FWD = BT_KINDS_ALL & ~(bt_kind(4) | bt_kind16(4) | bt_kind(5) | bt_kind16(5));
+// input-gradient form (dy W): plain, accumulate into dx, GELU' from either aux type
+constexpr int BT_KINDS_DGRAD = bt_kind(0) | bt_kind(2) | bt_kind(4) | bt_kind16(4);
+// weight-gradient form (dy^T x): plain, accumulate into dW
+constexpr int BT_KINDS_WGRAD = bt_kind(0) | bt_kind(2);
+
 // csum: the column sums of this part are ADDED to it (lane layout: the four columns nb + 4 (lane % (8 FN)) ..., one partial per row
 // group).  defer_colsum: nothing is flushed — the caller folds the parts of a whole workgroup tile and issues ONE atomic per column
 // (bt_tail); otherwise the wave folds its own row groups and adds its sums to p.out_colsum itself (csum should come in as zero).
-template <int FM, int FN>
+template <int FM, int FN, int KINDS = BT_KINDS_ALL>
 __device__ __forceinline__ void bt_wave_epilogue(const GArgs& p, int kind, int mb, int nb, const float* Tw, int lane, float& sqs, const f32x4 bias4,
                                                  f32x4& csum, const bool defer_colsum) {
     constexpr int LPR = 8 * FN;
     const bool full = mb + 32 * FM <= p.M && nb + 32 * FN <= p.N;
+    if constexpr (KINDS != BT_KINDS_ALL) {         // (wave-uniform; with the full set the switch is what it always was)
+        const int bit = kind + ((kind >= 3 && kind <= 5 && p.aux16) ? 8 : 0);
+        if (kind > 6 || !((KINDS >> bit) & 1)) kind = 7;
+    }
 #define VITAE_BT_ROWS(E)                                                                       \
     case E:                                                                                    \
-        if (full) bt_wave_rows<FM, FN, E, true, false>(p, mb, nb, Tw, lane, sqs, csum, bias4);  \
-        else bt_wave_rows<FM, FN, E, false, false>(p, mb, nb, Tw, lane, sqs, csum, bias4);      \
+        if constexpr ((KINDS & bt_kind(E)) != 0) {                                             \
+            if (full) bt_wave_rows<FM, FN, E, true, false>(p, mb, nb, Tw, lane, sqs, csum, bias4);  \
+            else bt_wave_rows<FM, FN, E, false, false>(p, mb, nb, Tw, lane, sqs, csum, bias4);      \
+        }                                                                                      \
         break;
 #define VITAE_BT_ROWS_AUX(E)                                                                   \
     case E:                                                                                    \
         if (p.aux16) {                                                                         \
-            if (full) bt_wave_rows<FM, FN, E, true, true>(p, mb, nb, Tw, lane, sqs, csum, bias4);  \
-            else bt_wave_rows<FM, FN, E, false, true>(p, mb, nb, Tw, lane, sqs, csum, bias4);      \
+            if constexpr ((KINDS & bt_kind16(E)) != 0) {                                       \
+                if (full) bt_wave_rows<FM, FN, E, true, true>(p, mb, nb, Tw, lane, sqs, csum, bias4);  \
+                else bt_wave_rows<FM, FN, E, false, true>(p, mb, nb, Tw, lane, sqs, csum, bias4);      \
+            }                                                                                  \
         } else {                                                                               \
-            if (full) bt_wave_rows<FM, FN, E, true, false>(p, mb, nb, Tw, lane, sqs, csum, bias4); \
-            else bt_wave_rows<FM, FN, E, false, false>(p, mb, nb, Tw, lane, sqs, csum, bias4);     \
+            if constexpr ((KINDS & bt_kind(E)) != 0) {                                         \
+                if (full) bt_wave_rows<FM, FN, E, true, false>(p, mb, nb, Tw, lane, sqs, csum, bias4); \
+                else bt_wave_rows<FM, FN, E, false, false>(p, mb, nb, Tw, lane, sqs, csum, bias4);     \
+            }                                                                                  \
         }                                                                                      \
         break;
     switch (kind) {

@@ -674,9 +674,11 @@ inline BtPlan bt_plan(int M, int N, int K, int a_kc, int b_kc, bool allow_split,
         const bool forced = g_bt_mode >= 0;
         if (!forced && (M < bm / 2 || N < bn / 2)) continue;
         const long tiles = (long)cdiv(M, bm) * cdiv(N, bn);
-        const int fsplit = ENV_INT_ONCE("VITAE_BT_SPLIT", 0);   // tools: with a forced tile, this split only
+        // tests, tools: with a forced tile, this split only (read per call, and only under a forced tile: a test runs one shape at
+        // several splits in one process); a launch that may not split — the pair's weight gradient — keeps its one range
+        const int fsplit = forced && allow_split ? env_int("VITAE_BT_SPLIT", 0) : 0;
         for (int s = 1; s <= (id >= 3 && allow_split ? (id == 6 ? 4 : 8) : 1); ++s) {
-            if (forced && fsplit > 0 && s != fsplit) continue;
+            if (fsplit > 0 && s != fsplit) continue;
             const int kps = cdiv(cdiv(K, s), BK) * BK;
             if (cdiv(K, kps) != s || kps < (forced ? 2 : 4) * BK || K - (s - 1) * kps < 2 * BK) continue;
             if (s > 1 && (tiles > VITAE_GLDS_TICKETS || (cap >= 0 && VITAE_GLDS_TICKETS + tiles * s * bm * bn > cap))) continue;

@@ -29,7 +29,10 @@ constexpr int WS64_SMEM = VITAE_WS64_STAGES * 16384;
 // fragment (the two fragments are the two independent MFMA chains): with the even / odd pair per fragment the weight-gradient form
 // with row sums needs 64 + 48 (fragments of four k-slices) + 16 registers before any address — over the 128 of two workgroups per CU.
 // So an output element is summed in k order, not in the 64 x 64 tile's even-then-odd order: equal to tile 5 to round-off, not bitwise.
-template <bool A_KC, bool B_KC, int S, bool RS, bool W2 = false, int BM = 64>
+// KINDS: the epilogue instantiations this body carries (gemm_bt.hpp, BT_KINDS_*).
+// ROLE: 0 = the workgroup's waves split into producers and consumers here; 1 / 2 = the caller has split them already and this
+// instantiation holds the producers' / the consumers' code only (gemm_ws64_pair_kernel: why is told there).
+template <bool A_KC, bool B_KC, int S, bool RS, bool W2 = false, int BM = 64, int KINDS = BT_KINDS_ALL, int ROLE = 0>
 __device__ __forceinline__ void gemm_ws64_body(const GArgs& p, const WsHot& h, const int bid, const int zid, unsigned char* smem) {
 #ifndef VITAE_WS64_PRODUCERS
 #define VITAE_WS64_PRODUCERS 4
@@ -57,7 +60,7 @@ __device__ __forceinline__ void gemm_ws64_body(const GArgs& p, const WsHot& h, c
     auto stamp = [&](int i) {
         if ((h.xcd_m & 2) && (threadIdx.x & 255) == 0) p.dbg[((long)blockIdx.z * gridDim.x + blockIdx.x) * 16 + i] = __builtin_amdgcn_s_memtime();
     };
-    if (wave >= NWC) {
+    if (ROLE != 2 && (ROLE == 1 || wave >= NWC)) {
         // ---------------- producers ----------------
         const int pw = wave - NWC;
         stamp(8);
@@ -239,7 +242,7 @@ __device__ __forceinline__ void gemm_ws64_body(const GArgs& p, const WsHot& h, c
     bt_park_quadrant<FM, 1, 1>(accs, lane, Tw);
     __builtin_amdgcn_wave_barrier();
     float sqs = 0.f;
-    { f32x4 cz = {0.f, 0.f, 0.f, 0.f}; bt_wave_epilogue<FM, 1>(p, bt_epilogue_kind(p), m0 + wm * (BM / 2), n0 + wn * 32, Tw, lane, sqs, bias4, cz, false); }
+    { f32x4 cz = {0.f, 0.f, 0.f, 0.f}; bt_wave_epilogue<FM, 1, KINDS>(p, bt_epilogue_kind(p), m0 + wm * (BM / 2), n0 + wn * 32, Tw, lane, sqs, bias4, cz, false); }
     stamp(5);                                                            // stores issued
     if (p.sqacc) {                                                       // one atomic per workgroup (see bt_tail)
         sqs = wave_sum(sqs);
@@ -251,11 +254,14 @@ __device__ __forceinline__ void gemm_ws64_body(const GArgs& p, const WsHot& h, c
     if (p.dbg) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(6); }      // stores drained
 }
 
+// the epilogue set of an operand form: forward (both k-contiguous), input gradient (A k-contiguous), weight gradient (neither)
+template <bool A_KC, bool B_KC> constexpr int ws64_kinds() { return A_KC && B_KC ? BT_KINDS_FWD : A_KC ? BT_KINDS_DGRAD : BT_KINDS_WGRAD; }
+
 template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(64 * (4 + VITAE_WS64_PRODUCERS), 2) void gemm_ws64_kernel(WS_HOT_PARAMS, const GArgs p) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[WS64_SMEM];      // the ONLY LDS object
     const WsHot h = WS_HOT_FROM_PARAMS;
-    gemm_ws64_body<A_KC, B_KC, VITAE_WS64_STAGES, false>(p, h, blockIdx.x, blockIdx.z, smem);
+    gemm_ws64_body<A_KC, B_KC, VITAE_WS64_STAGES, false, false, 64, ws64_kinds<A_KC, B_KC>()>(p, h, blockIdx.x, blockIdx.z, smem);
 }
 
 // the 128 x 64 tile (id 7): [A 16 KB | B 8 KB] per stage, three stages = 72 KB, two workgroups per CU
@@ -264,7 +270,7 @@ template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(64 * (4 + VITAE_WS64_PRODUCERS), 2) void gemm_ws64_m128_kernel(WS_HOT_PARAMS, const GArgs p) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[WS128X64_SMEM];  // the ONLY LDS object
     const WsHot h{A, B, B2, lda, ldb, M, N, K, (M + 127) >> 7, (N + 63) >> 6, xcd_m, kps};
-    gemm_ws64_body<A_KC, B_KC, WS128X64_STAGES, false, false, 128>(p, h, blockIdx.x, blockIdx.z, smem);
+    gemm_ws64_body<A_KC, B_KC, WS128X64_STAGES, false, false, 128, ws64_kinds<A_KC, B_KC>()>(p, h, blockIdx.x, blockIdx.z, smem);
 }
 
 // id: 5 (64 x 64) or 7 (128 x 64); p.tiles_m / p.tiles_n are that tile's counts (bt_launch)
@@ -284,7 +290,7 @@ void ws64_launch(const GArgs& p, int a_kc, int b_kc, int id, hipStream_t st) {
 constexpr int WS64W2_STAGES = 3;           // [A | B hi | B lo] = 24 KB per stage: three stages = 72 KB, two workgroups per CU
 __global__ __launch_bounds__(64 * (4 + VITAE_WS64_PRODUCERS), 2) void gemm_ws64_w2_kernel(WS_HOT_PARAMS, const GArgs p) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[WS64W2_STAGES * 24576];      // the ONLY LDS object
-    gemm_ws64_body<true, true, WS64W2_STAGES, false, true>(p, WS_HOT_FROM_PARAMS, blockIdx.x, blockIdx.z, smem);
+    gemm_ws64_body<true, true, WS64W2_STAGES, false, true, 64, BT_KINDS_FWD>(p, WS_HOT_FROM_PARAMS, blockIdx.x, blockIdx.z, smem);
 }
 
 // p: a complete forward-form descriptor (both operands k-contiguous, vec_epi set, p.B2 = the lo plane, p.splits k-ranges)
@@ -304,36 +310,50 @@ int ws64_w2_launch(GArgs p, hipStream_t st) {
 // The leading scalars are what either half needs before its first DMA (WsHot), in 14 dwords so that all of them are preloaded: the
 // halves of one Linear's backward SHARE dy (A of both), its leading dimension, the leading dimension of W / x, the width K of the layer
 // (N of both), and the weight gradient's rows are the input gradient's reduction length (ws64_pair_launch checks exactly that).
-//   packed = nb1 | p1.splits << 20 | p1.xcd_m << 24 | p2.xcd_m << 25 | (dbg set) << 26
-// BM1 / BM2: the rows of either half's tile (64: tile 5, 128: tile 7), chosen independently; the LDS is the larger need of the two.
-template <bool RS, int BM1, int BM2>
+//   packed = nb1 | p1.splits << 20 | p1.xcd_m << 24 | p2.xcd_m << 25 | (dbg set) << 26 | (128-row input gradient) << 27 | (128-row weight gradient) << 28
+// ONE image for every pair launch of a step: the rows of either half's tile (64: tile 5, 128: tile 7) travel in `packed`, and
+// wave-uniform branches (a kernel argument and blockIdx: scalar) select among FOUR bodies, each instantiated once — 64-row and
+// 128-row input gradient, 64-row and 128-row weight gradient, each as its producers' and its consumers' part — with the epilogue
+// sets of their forms (BT_KINDS_DGRAD / _WGRAD).
+// The row sums are a run-time property of both weight-gradient bodies (p2.a_rowsum; the predicate was wave-uniform and run-time
+// already: the MFMAs against ones sit behind it).  As <RS, BM1, BM2> instantiations there were eight kernels of 265-512 KB whose
+// sixteen inlined bodies each carried all 22 epilogue instantiations.
+// LDS: the 72 KB of the 128-row geometry, static; the 64-row bodies keep their four 16 KB stages inside it.  Two workgroups per CU.
+// p1 / p2 go to the bodies directly in the if / else chain (a select over two by-value descriptors: LABNOTES.md, round 6).
 __global__ __launch_bounds__(64 * (4 + VITAE_WS64_PRODUCERS), 2) void gemm_ws64_pair_kernel(const __bf16* A, const __bf16* B1, const __bf16* B2, int lda, int ldb,
                                                                                            int M1, int N1, int K1, int K2, int kps1, int packed,
                                                                                            const GArgs p1, const GArgs p2) {
-    constexpr int S1 = BM1 == 128 ? WS128X64_STAGES : VITAE_WS64_STAGES, S2 = BM2 == 128 ? WS128X64_STAGES : VITAE_WS64_STAGES;
-    constexpr int SMEM = (BM1 == 128 || BM2 == 128) ? WS128X64_SMEM : WS64_SMEM;
-    static_assert(SMEM >= WS64_SMEM && 2 * SMEM <= 160 * 1024, "either body's stages; two workgroups per CU");
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM];
+    static_assert(WS128X64_SMEM >= WS64_SMEM && 2 * WS128X64_SMEM <= 160 * 1024, "either body's stages; two workgroups per CU");
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[WS128X64_SMEM];
     const int nb1 = packed & 0xfffff, splits1 = (packed >> 20) & 15, dbg2 = (packed >> 25) & 2;
-    if ((int)blockIdx.x < nb1 * splits1) {
-        const WsHot h{A, B1, nullptr, lda, ldb, M1, N1, K1, (M1 + BM1 - 1) >> (BM1 == 128 ? 7 : 6), (N1 + 63) >> 6, ((packed >> 24) & 1) | dbg2, kps1};
-        gemm_ws64_body<true, false, S1, false, false, BM1>(p1, h, blockIdx.x % nb1, blockIdx.x / nb1, smem);
-    } else {
-        const WsHot h{A, B2, nullptr, lda, ldb, K1, N1, K2, (K1 + BM2 - 1) >> (BM2 == 128 ? 7 : 6), (N1 + 63) >> 6, ((packed >> 25) & 1) | dbg2, K2};
-        gemm_ws64_body<false, false, S2, RS, false, BM2>(p2, h, blockIdx.x - nb1 * splits1, 0, smem);
+    // The producer / consumer split comes FIRST, the half and its row count after it, so that no use of p1 / p2 is on the producers'
+    // path: both row counts of a half read the same descriptor, and hipcc places those scalar loads (and their s_waitcnt, twice)
+    // in front of the branch that the uses have in common.  With the row-count branch outermost that was in front of the tile
+    // decode and the first DMA of every workgroup: every pair launch of the step 0.4-0.6 us longer (profiles/pair_image_*).
+#define VITAE_WS64_PAIR_HALVES(ROLE)                                                                                                              \
+    if ((int)blockIdx.x < nb1 * splits1) {                                                                                                        \
+        if ((packed >> 27) & 1) {                                                                                                                 \
+            const WsHot h{A, B1, nullptr, lda, ldb, M1, N1, K1, (M1 + 127) >> 7, (N1 + 63) >> 6, ((packed >> 24) & 1) | dbg2, kps1};             \
+            gemm_ws64_body<true, false, WS128X64_STAGES, false, false, 128, BT_KINDS_DGRAD, ROLE>(p1, h, blockIdx.x % nb1, blockIdx.x / nb1, smem); \
+        } else {                                                                                                                                  \
+            const WsHot h{A, B1, nullptr, lda, ldb, M1, N1, K1, (M1 + 63) >> 6, (N1 + 63) >> 6, ((packed >> 24) & 1) | dbg2, kps1};              \
+            gemm_ws64_body<true, false, VITAE_WS64_STAGES, false, false, 64, BT_KINDS_DGRAD, ROLE>(p1, h, blockIdx.x % nb1, blockIdx.x / nb1, smem); \
+        }                                                                                                                                         \
+    } else {                                                                                                                                      \
+        if ((packed >> 28) & 1) {                                                                                                                 \
+            const WsHot h{A, B2, nullptr, lda, ldb, K1, N1, K2, (K1 + 127) >> 7, (N1 + 63) >> 6, ((packed >> 25) & 1) | dbg2, K2};               \
+            gemm_ws64_body<false, false, WS128X64_STAGES, true, false, 128, BT_KINDS_WGRAD, ROLE>(p2, h, blockIdx.x - nb1 * splits1, 0, smem);    \
+        } else {                                                                                                                                  \
+            const WsHot h{A, B2, nullptr, lda, ldb, K1, N1, K2, (K1 + 63) >> 6, (N1 + 63) >> 6, ((packed >> 25) & 1) | dbg2, K2};                \
+            gemm_ws64_body<false, false, VITAE_WS64_STAGES, true, false, 64, BT_KINDS_WGRAD, ROLE>(p2, h, blockIdx.x - nb1 * splits1, 0, smem);   \
+        }                                                                                                                                         \
     }
-}
-
-template <bool RS>
-static void ws64_pair_dispatch(int bm1, int bm2, dim3 grid, dim3 block, hipStream_t st, const GArgs& p1, const GArgs& p2, int packed) {
-#define VITAE_WS64_PAIR(B1, B2)                                                                                                              \
-    hipLaunchKernelGGL((gemm_ws64_pair_kernel<RS, B1, B2>), grid, block, 0, st, p1.A, p1.B, p2.B, (int)p1.lda, (int)p1.ldb, p1.M, p1.N, p1.K, \
-                       p2.K, p1.k_per_split, packed, p1, p2)
-    if (bm1 == 64 && bm2 == 64) VITAE_WS64_PAIR(64, 64);
-    else if (bm1 == 64) VITAE_WS64_PAIR(64, 128);
-    else if (bm2 == 64) VITAE_WS64_PAIR(128, 64);
-    else VITAE_WS64_PAIR(128, 128);
-#undef VITAE_WS64_PAIR
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= 4) {
+        VITAE_WS64_PAIR_HALVES(1)
+    } else {
+        VITAE_WS64_PAIR_HALVES(2)
+    }
+#undef VITAE_WS64_PAIR_HALVES
 }
 
 // p1 / p2: complete descriptors of the two halves (vec_epi set, K % 64 == 0); p1.splits k-ranges of >= 2 k-tiles each;
@@ -352,9 +372,10 @@ int ws64_pair_launch(GArgs p1, GArgs p2, hipStream_t st, int bm1, int bm2) {
     // what the kernel's leading scalars assume (the two halves of ONE Linear's backward: gemm_ws64_pair_kernel)
     if (p1.A != p2.A || p1.lda != p2.lda || p1.ldb != p2.ldb || p2.M != p1.K || p2.N != p1.N || nb1 >= (1 << 20) || p1.splits > 15 ||
         p1.lda >= (1L << 31) || p1.ldb >= (1L << 31)) return VITAE_ERR_UNSUPPORTED_SHAPE;
-    const int packed = nb1 | p1.splits << 20 | (p1.xcd_m & 1) << 24 | (p2.xcd_m & 1) << 25 | ((p1.dbg || p2.dbg) ? 1 << 26 : 0);
-    if (p2.a_rowsum) ws64_pair_dispatch<true>(bm1, bm2, grid, block, st, p1, p2, packed);
-    else ws64_pair_dispatch<false>(bm1, bm2, grid, block, st, p1, p2, packed);
+    const int packed = nb1 | p1.splits << 20 | (p1.xcd_m & 1) << 24 | (p2.xcd_m & 1) << 25 | ((p1.dbg || p2.dbg) ? 1 << 26 : 0) |
+                       (bm1 == 128 ? 1 << 27 : 0) | (bm2 == 128 ? 1 << 28 : 0);
+    hipLaunchKernelGGL(gemm_ws64_pair_kernel, grid, block, 0, st, p1.A, p1.B, p2.B, (int)p1.lda, (int)p1.ldb, p1.M, p1.N, p1.K, p2.K, p1.k_per_split,
+                       packed, p1, p2);
     return vitae_launch_status();
 }
 
